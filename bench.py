@@ -179,6 +179,20 @@ def run_step(model, outs, ops, allreduce, dependent=True):
             i += 1
 
 
+def dump_outputs(path, model, outs):
+    """--dump-outputs: what the last timed step computed -- every Linear's output, in step order -- as path/layerNN_<name>.npy
+    (float32; the outputs are fp16, so the conversion is exact).  The inputs are seeded (build_model), so two builds of the project
+    run with the same arguments can be compared output for output."""
+    import numpy as np
+
+    names = [f"layer{li:02d}_{lin['name']}" for li, layer in enumerate(model) for lin in layer]
+    total = sum(o.numel() * 4 for o in outs)
+    assert len(names) == len(outs) and total <= 64 << 20, f"{total / 2**20:.1f} MB of outputs: over the 64 MB of --dump-outputs"
+    os.makedirs(path, exist_ok=True)
+    for name, o in zip(names, outs):
+        np.save(os.path.join(path, name + ".npy"), o.float().cpu().numpy())
+
+
 def unit_gain(model, ops, world=1):
     """Scale every Linear's scales so that its output has unit rms on a unit-rms input (random packed weights have a gain of ~10 per
     link: fp16 would overflow after a few links of the dependent chain).  Row-parallel Linears (their outputs are summed over the
@@ -682,6 +696,8 @@ def dry_run(a):
         run_step(model, outs, ops, allreduce)
     dist.barrier()
     t = torch.tensor([(time.perf_counter() - t0) * 1e3])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, outs)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     # every row-parallel output went through the collective: each element is the sum of (rank + 1) over the ranks
     reduced = [o for o, lin in zip(outs, (l for layer in model for l in layer)) if lin["reduce"]]
@@ -719,7 +735,12 @@ def main():
                     help="no GPU: the multi-rank plumbing only (rendezvous over gloo, per-rank shard shapes, the collective's rank-"
                          "consistent fallback, barrier + max-over-ranks timing) with launches replaced by zero outputs; prints a line "
                          "marked dry_run whose value is null (tests/test_tp_cpu.py runs it with two processes)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (every Linear's output of the headline step; rank 0's "
+                         "with --gpus > 1) as DIR/layerNN_<name>.npy, float32")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.dry_run:
         return dry_run(a)
 
@@ -799,6 +820,7 @@ def main():
         ms_total = e0.elapsed_time(e1)
         if oneshot is not None:
             oneshot.check()  # a rank that gave up on a peer wrote NaN and raised the sticky word: the timing would be meaningless
+        last_outs = [o.cpu() for o in outs] if a.dump_outputs and rank == 0 else None  # before any later replay (sustained) runs
         sustained = None
         if world == 1 and not a.no_secondary:  # the same replay for >= 1 s: a leg the GPU-busy sampler of the driver can see
             t_end, n_sus = time.perf_counter() + 1.2, 0
@@ -823,6 +845,8 @@ def main():
     else:
         bytes_all = float(bytes_step)
     ms_step = ms_total / a.steps
+    if last_outs is not None:
+        dump_outputs(a.dump_outputs, model, last_outs)
 
     if rank == 0:
         tok_s = 1000.0 / ms_step

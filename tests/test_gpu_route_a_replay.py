@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 import torch
+from test_route_a import fixture_array
 
 pytestmark = pytest.mark.gpu
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "route_a_calls.npz")
@@ -50,7 +51,7 @@ def test_reference_call_replayed_on_hip(i):
     args = []
     for a in e["args"]:
         if "t" in a:
-            args.append(torch.from_numpy(np.ascontiguousarray(d[a["t"]])).cuda())
+            args.append(torch.from_numpy(np.ascontiguousarray(fixture_array(d, a["t"]))).cuda())
         elif "none" in a:
             args.append(None)
         else:
@@ -61,9 +62,9 @@ def test_reference_call_replayed_on_hip(i):
     pairs = []
     if e["ret"] is not None:
         assert torch.is_tensor(ret), f'{e["fn"]}: the reference expects a tensor back'
-        pairs.append((ret, d[e["ret"]["t"]], "return value"))
+        pairs.append((ret, fixture_array(d, e["ret"]["t"]), "return value"))
     for j, m in e["mutated"].items():
-        pairs.append((args[int(j)], d[m["t"]], f"argument {j} (written by the call)"))
+        pairs.append((args[int(j)], fixture_array(d, m["t"]), f"argument {j} (written by the call)"))
     for got, want, what in pairs:
         assert tuple(got.shape) == tuple(want.shape), (e["fn"], what, tuple(got.shape), want.shape)
         g = got.cpu().numpy()

@@ -1,6 +1,6 @@
 """Every `awq_ext` / `awq_v2_ext` shim entry point on the GPU kernels, called with the reference's positional
-forms (the call sites are cited; the reference's own modules running over these shims are in
-tests/test_route_a.py, which needs /root/reference and therefore runs in the build container only)."""
+forms (the call sites are cited; the calls the reference's own modules make into these shims are replayed in
+tests/test_route_a.py on CPU and tests/test_gpu_route_a_replay.py on the GPU)."""
 import numpy as np
 import pytest
 import torch
