@@ -33,6 +33,20 @@ class AwqGemvEx(ctypes.Structure):
                 ("stream", c_void_p), ("norm_weight", c_void_p), ("norm_eps", c_float), ("add_residual", c_void_p)]
 
 
+class AwqSampleParams(ctypes.Structure):
+    """struct AwqSampleParams of include/awq_hip.h (same field order; lives in device memory)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("do_sample", ctypes.c_int32), ("temperature", c_float), ("top_k", ctypes.c_int32),
+                ("top_p", c_float), ("n_eos", ctypes.c_int32), ("pad", ctypes.c_int32), ("eos", ctypes.c_int32 * 8)]
+
+
+class AwqSampleArgs(ctypes.Structure):
+    """struct AwqSampleArgs of include/awq_hip.h (same field order)."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("logits", c_void_p), ("B", c_int64),
+                ("V", c_int64), ("row_stride", c_int64), ("params", c_void_p), ("t", c_void_p), ("out", c_void_p),
+                ("out_stride", c_int64), ("ring", c_void_p), ("ring_cap", c_int64), ("finished", c_void_p), ("status", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol include/awq_hip.h declares
 # (tests/test_boundary.py cross-checks this table against the header and the .so).
 SIGNATURES = {
@@ -93,6 +107,8 @@ SIGNATURES = {
                                                  c_void_p]),
     "awq_gemm_workspace_status": (c_int, [c_void_p, c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "awq_gemm_auto_kernel": (c_int, [c_int64, c_int64, c_int64, c_int64]),
+    "awq_sample_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "awq_sample_tokens": (c_int, [ctypes.POINTER(AwqSampleArgs)]),
 }
 
 

@@ -20,9 +20,17 @@ ONCE and replayed:
     logits = dec.prefill(prompt_ids)          # eager, any length
     for _ in range(n):
         logits = dec.step(next_ids)           # [batch, 1, vocab]; valid until the next step
+
+Token generation (`generate`) replays a second family of graphs: the same step, then the sampler (csrc/sample.hip) writing
+the next ids straight into the step's input buffer, a ring of generated tokens and the per-row finished flags.  The host only
+picks buckets, rolls the window and looks at the flags every `check_every` tokens.
+
+    out = dec.generate(prompt_ids, max_new_tokens=64, do_sample=True, top_p=0.9, seed=1)   # [batch, prompt + n] int64
 """
 import torch
 
+from ... import ops
+from ..._lib import AwqHipError
 from .model import StepPlan
 
 
@@ -58,6 +66,8 @@ class GraphedDecoder:
             self.tok = torch.zeros((self.batch, 1), dtype=torch.int64, device=self.device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.graphs = {}  # bucket bound -> (graph, logits)
+        self.gen_graphs = {}  # (bucket bound, greedy) -> (graph, logits): step + sampler (generate)
+        self._gen = None  # generate's device words (allocated by its first call)
         self.position = 0
         for b in self.blocks:
             b.attn._resize_cache(self.batch)
@@ -96,7 +106,7 @@ class GraphedDecoder:
 
     # ---- one token ------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
-    def _capture(self, bound):
+    def _capture(self, bound, sample=None):
         for b in self.blocks:
             b.attn.use_device_positions(self.pos, self.len)
             b.attn.decode_len_bound = bound
@@ -112,6 +122,8 @@ class GraphedDecoder:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=self.stream):
                 logits = self.lm(self.tok)
+                if sample is not None:
+                    sample(logits)
                 self.pos.add_(1)
                 self.len.add_(1)
             self.stream.synchronize()
@@ -119,17 +131,26 @@ class GraphedDecoder:
             self.len.copy_(keep[1])
         caller.wait_stream(self.stream)
         self._sync_host_state()
+        if sample is not None:
+            return graph, logits
         self.graphs[bound] = (graph, logits)
         return self.graphs[bound]
 
-    def _advance(self):
+    def _advance(self, greedy=None):
         """What `step` and `replay` share: roll a full window, pick (or capture) the bucket's graph, replay it on the decoder's stream
-        between the caller's work, advance the position on the host as the graph did on the device."""
+        between the caller's work, advance the position on the host as the graph did on the device.  greedy = True / False:
+        the generation graph (step + sampler) instead of the step graph."""
         if self.position + 1 > self.max_seq_len:  # past the window: forget the oldest positions (eagerly)
             live = [b.attn.cache.roll_kv_n_steps(self.position, n=StepPlan.ROLL) for b in self.blocks][0]
             self.seek(live)
         bound = self.bucket(self.position + 1)
-        graph, logits = self.graphs.get(bound) or self._capture(bound)
+        if greedy is None:
+            graph, logits = self.graphs.get(bound) or self._capture(bound)
+        else:
+            key = (bound, bool(greedy))
+            if key not in self.gen_graphs:
+                self.gen_graphs[key] = self._capture(bound, sample=lambda lg: self._sample(lg, greedy))
+            graph, logits = self.gen_graphs[key]
         caller = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(caller)   # the ids were copied on the caller's stream
         with torch.cuda.stream(self.stream):
@@ -151,3 +172,80 @@ class GraphedDecoder:
         """The current bucket's graph once more on the decoder's stream with the ids already in place (benchmarks: no host
         copies in the timed region).  Same roll / stream / host bookkeeping as `step`."""
         return self._advance()
+
+    # ---- generation: sampler in the graph ---------------------------------------------------------------------------------
+    def _gen_state(self, vocab, cap):
+        """The device words generate owns.  Their addresses are baked into the generation graphs: reallocated (and the graphs
+        dropped) only when the vocabulary or the ring capacity has to grow."""
+        g = self._gen
+        if g is not None and g["vocab"] == vocab and g["ring"].shape[1] >= cap:
+            return g
+        with torch.inference_mode(False):
+            dev = self.device
+            g = {"vocab": vocab,
+                 "params": torch.zeros(64, dtype=torch.uint8, device=dev),
+                 "t": torch.ones(1, dtype=torch.int32, device=dev),
+                 "ring": torch.zeros((self.batch, max(int(cap), 256)), dtype=torch.int32, device=dev),
+                 "finished": torch.zeros(self.batch, dtype=torch.int32, device=dev),
+                 "status": torch.zeros((self.batch + 31) // 32, dtype=torch.int32, device=dev),
+                 "ws": torch.zeros(ops.sample_workspace_bytes(self.batch, vocab), dtype=torch.uint8, device=dev)}
+        self.gen_graphs = {}
+        self._gen = g
+        return g
+
+    def _sample(self, logits, greedy):
+        g = self._gen
+        ops.sample_launch(logits, g["params"], g["t"], self.tok.view(-1), g["status"], g["ws"], ring=g["ring"],
+                          finished=g["finished"], greedy=greedy)
+
+    def _check(self, g):
+        st = g["status"].cpu()
+        if bool(st.any()):
+            bad = [r for r in range(self.batch) if (int(st[r // 32]) >> (r % 32)) & 1]
+            raise AwqHipError(f"generate: rows {bad} produced NaN / +inf logits or kept no token")
+        return bool(g["finished"].cpu().all())
+
+    @torch.inference_mode()
+    def generate(self, input_ids, max_new_tokens, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                 eos_token_id=None, pad_token_id=None, check_every=16):
+        """input_ids [batch, prompt] -> [batch, prompt + n] int64 on the device, n <= max_new_tokens; rows that emitted an EOS id
+        are padded with pad_token_id (default: the first EOS id) from then on, and the run stops once every row has (HF's
+        `generate` semantics).  The prompt is prefilled eagerly and token 1 sampled eagerly from its last position; every later
+        token is one replay of the bucket's generation graph.  The host reads the finished flags and the status word once
+        every `check_every` tokens -- no host sync per token.  Sampling as ops.sample_tokens: temperature, top_k, top_p,
+        Gumbel-max draw with Philox numbers keyed by (seed, token index, row)."""
+        input_ids = input_ids.to(self.device)
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
+            raise ValueError(f"input_ids must be [{self.batch}, prompt], got {tuple(input_ids.shape)}")
+        max_new_tokens, check_every = int(max_new_tokens), max(1, int(check_every))
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+        params = ops.sample_params(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, eos_ids=eos,
+                                   pad=pad_token_id)
+        greedy = not do_sample or float(temperature) <= 0
+        logits = self.prefill(input_ids)
+        g = self._gen_state(logits.shape[-1], max_new_tokens)
+        # reset every decoder-owned device word, outside any capture
+        g["params"].copy_(params)
+        g["t"].fill_(1)
+        g["ring"].zero_()
+        g["finished"].zero_()
+        g["status"].zero_()
+        self._sample(logits, greedy)  # token 1, eagerly, into self.tok
+        n = 1
+        while n < max_new_tokens:
+            if n % check_every == 0 and self._check(g):
+                break
+            self._advance(greedy=greedy)  # step on token n, sample token n + 1
+            n += 1
+        done = self._check(g)
+        new = g["ring"][:, :n]
+        if done and eos:  # HF stops at the step where the last row finished: drop the all-pad columns after it
+            hit = torch.zeros_like(new, dtype=torch.bool)
+            for e in eos:
+                hit |= new == e
+            first = torch.where(hit.any(1), hit.int().argmax(1), torch.full_like(hit[:, 0], n, dtype=torch.int64))
+            n = min(n, int(first.max()) + 1)
+            new = new[:, :n]
+        return torch.cat([input_ids.long(), new.long()], dim=1)

@@ -861,3 +861,131 @@ def gemm_forward_ex(x2d, qweight, scales, qzeros, bias=None, flags=0, norm_weigh
         rc = L.awq_gemm_forward_ex(ctypes.byref(e))
     _lib.check(rc, "awq_gemm_forward_ex")
     return y, ssq
+
+
+# ---- token selection (csrc/sample.hip) --------------------------------------------------------------------------------
+SAMPLE_FLAG_GREEDY = 1  # AWQ_SAMPLE_FLAG_GREEDY
+SAMPLE_MAX_EOS = 8
+_sample_workspaces = {}  # (device index, stream handle) -> zeroed uint8 tensor (every call leaves it zero)
+
+
+def sample_params(*, do_sample, temperature=1.0, top_k=0, top_p=1.0, seed=0, eos_ids=(), pad=None):
+    """Validate a sampling configuration and pack it as struct AwqSampleParams: a 64-byte CPU uint8 tensor the caller copies
+    to the device (the kernel reads its parameters from device memory).  pad defaults to the first EOS id, else 0."""
+    temperature, top_p, top_k = float(temperature), float(top_p), int(top_k)
+    if top_k < 0:
+        raise ValueError(f"top_k must be >= 0 (0 = off), got {top_k}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must be in (0, 1] (1 = off), got {top_p}")
+    if temperature != temperature:
+        raise ValueError("temperature is NaN")
+    eos = [int(e) for e in (eos_ids if eos_ids is not None else ())]
+    if len(eos) > SAMPLE_MAX_EOS:
+        raise ValueError(f"at most {SAMPLE_MAX_EOS} EOS ids, got {len(eos)}")
+    if pad is None:
+        pad = eos[0] if eos else 0
+    p = _lib.AwqSampleParams()
+    p.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    p.do_sample = 1 if do_sample else 0
+    p.temperature = temperature
+    p.top_k = min(top_k, 0x7FFFFFFF)
+    p.top_p = top_p
+    p.n_eos = len(eos)
+    p.pad = int(pad)
+    for i, e in enumerate(eos):
+        p.eos[i] = e
+    return torch.frombuffer(bytearray(bytes(p)), dtype=torch.uint8)
+
+
+def sample_workspace_bytes(B, V):
+    return int(_lib.lib().awq_sample_workspace_bytes(B, V))
+
+
+def _sample_workspace(device, nbytes):
+    key = (device.index if device.index is not None else torch.cuda.current_device(), _stream())
+    ws = _sample_workspaces.get(key)
+    if ws is None or ws.numel() < nbytes:
+        if ws is not None:
+            _retired_raw.append(ws)  # a captured graph may still hold it
+        with torch.inference_mode(False):
+            ws = torch.zeros(max(int(nbytes), 1 << 16), dtype=torch.uint8, device=device)
+        _sample_workspaces[key] = ws
+    return ws
+
+
+def _logits_rows(logits):
+    """[B, V] or [B, T, V] (the last position) fp16 with unit element stride -> (view [B, V], row stride)."""
+    if logits.dtype != torch.float16 or logits.dim() not in (2, 3):
+        raise _lib.AwqHipError(f"sample_tokens: fp16 logits [B, V] or [B, T, V] expected, got {logits.dtype} {tuple(logits.shape)}")
+    rows = logits[:, -1, :] if logits.dim() == 3 else logits
+    if rows.stride(1) != 1:
+        rows = rows.contiguous()
+    return rows, rows.stride(0)
+
+
+def sample_launch(logits, params, t, out, status, workspace, ring=None, finished=None, greedy=False):
+    """The raw launch (no validation of the configuration, no sync): every buffer a device tensor the caller owns --
+    params (64 bytes, sample_params), t (int32 [1]), out (int64, one element per row, any row stride), status (int32,
+    ceil(B / 32) words), workspace (zeroed once), ring (int32 [B, cap]) and finished (int32 [B]) optional.  Capturable."""
+    rows, rs = _logits_rows(logits)
+    B, V = rows.shape
+    _require_gpu(rows, params, t, out, status, workspace, ring, finished)
+    if out.numel() < B or status.numel() * 32 < B or (finished is not None and finished.numel() < B):
+        raise _lib.AwqHipError("sample_launch: out / status / finished too small for the batch")
+    if ring is not None and (ring.dim() != 2 or ring.shape[0] != B or not ring.is_contiguous() or ring.dtype != torch.int32):
+        raise _lib.AwqHipError("sample_launch: ring must be a contiguous int32 [B, cap] tensor")
+    if out.dtype != torch.int64 or t.dtype != torch.int32 or (finished is not None and finished.dtype != torch.int32):
+        raise _lib.AwqHipError("sample_launch: out int64, t and finished int32 expected")
+    a = _lib.AwqSampleArgs()
+    a.struct_bytes = ctypes.sizeof(_lib.AwqSampleArgs)
+    a.flags = SAMPLE_FLAG_GREEDY if greedy else 0
+    a.logits, a.B, a.V, a.row_stride = _ptr(rows), B, V, rs
+    a.params, a.t = _ptr(params), _ptr(t)
+    a.out, a.out_stride = _ptr(out), out.stride(0) if out.dim() else 1
+    a.ring, a.ring_cap = _ptr(ring), ring.shape[1] if ring is not None else 0
+    a.finished, a.status = _ptr(finished), _ptr(status)
+    a.workspace, a.workspace_bytes = _ptr(workspace), workspace.numel()
+    with torch.cuda.device(rows.device):
+        a.stream = _stream()
+        rc = _lib.lib().awq_sample_tokens(ctypes.byref(a))
+    _lib.check(rc, "awq_sample_tokens")
+    return out
+
+
+def sample_tokens(logits, *, do_sample, temperature=1.0, top_k=0, top_p=1.0, seed=0, t=1, eos_ids=(), pad=None, out=None,
+                  ring=None, finished=None, status=None):
+    """One token per row of fp16 logits [B, V] (or the last position of [B, T, V]), chosen on the device by
+    csrc/sample.hip: greedy argmax (ties to the lowest index), or temperature -> top-k -> top-p -> Gumbel-max draw with
+    Philox4x64-10 numbers keyed by (seed, t, row).  t is the 1-based index of the generated token (an int, or an int32 [1]
+    device word the launch advances by one).  Returns out (int64 [B]).  ring (int32 [B, cap]) receives the token at column
+    t - 1; finished (int32 [B]) latches on an EOS id, after which the row emits pad.  Without `status` the call waits for
+    the result and raises AwqHipError if a row held NaN / +inf or kept nothing; with an int32 status tensor the bits are
+    left there (sticky) and the call does not synchronise."""
+    params = sample_params(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, eos_ids=eos_ids,
+                           pad=pad)
+    if not isinstance(t, torch.Tensor) and int(t) < 1:
+        raise ValueError(f"t is the 1-based token index, got {t}")
+    rows, _ = _logits_rows(logits)
+    _require_gpu(rows)
+    B, V = rows.shape
+    dev = rows.device
+    need = sample_workspace_bytes(B, V)
+    if need == 0:
+        err = _lib.AwqHipError(f"sample_tokens: no kernel for B = {B}, V = {V} (limits B <= 1024, V <= 2^20)")
+        err.code = _lib.ERR_UNSUPPORTED
+        raise err
+    with torch.cuda.device(dev):
+        params_d = params.to(dev, non_blocking=False)
+        t_d = t if isinstance(t, torch.Tensor) else torch.tensor([int(t)], dtype=torch.int32, device=dev)
+        if out is None:
+            out = torch.empty(B, dtype=torch.int64, device=dev)
+        own_status = status is None
+        if own_status:
+            status = torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev)
+        ws = _sample_workspace(dev, need)
+        sample_launch(rows, params_d, t_d, out, status, ws, ring=ring, finished=finished, greedy=not do_sample or temperature <= 0)
+        if own_status:
+            bad = [r for r in range(B) if (int(status[r // 32].item()) >> (r % 32)) & 1] if bool(status.any()) else []
+            if bad:
+                raise _lib.AwqHipError(f"sample_tokens: rows {bad} hold NaN / +inf logits or keep no token (emitted pad)")
+    return out

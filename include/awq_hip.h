@@ -476,6 +476,56 @@ AWQ_EXPORT int awq_allreduce_ipc_export(void* ptr, void* handle64);
 AWQ_EXPORT int awq_allreduce_ipc_open(const void* handle64, void** ptr);
 AWQ_EXPORT int awq_allreduce_ipc_close(void* ptr);
 
+/* ---- token selection (csrc/sample.hip; the reference leaves it to transformers' generate: examples/generate.py) ----------
+ * One token per row of fp16 logits [B, V] (row_stride elements apart), entirely on the device; capturable, no sync, no
+ * allocation.  Greedy (do_sample == 0 or temperature <= 0): argmax, ties to the lowest index.  Sampling: temperature, then
+ * top_k (0 = off; boundary ties kept), then top_p (1 = off; the largest threshold whose tokens carry >= top_p of the
+ * softmax over the top-k set; a tied boundary group is kept whole), then a Gumbel-max draw with Philox4x64-10 numbers:
+ * u_i = word i % 4 of Philox4x64-10(key = (seed, 0), counter = (t, row, i / 4, 0)), u = ((w >> 41) + 0.5) * 2^-23
+ * (exact in fp32: 0 < u < 1, so every Gumbel term is finite).
+ * -inf logits are never kept; a row with NaN / +inf, or with nothing kept, sets bit (row % 32) of status[row / 32] (sticky:
+ * the caller clears it) and emits pad.  The launch writes out[row * out_stride] (int64), ring[row * ring_cap + t - 1] (int32,
+ * optional), latches finished[row] (int32, optional) when a SAMPLED token is an EOS id -- a finished row emits pad from then on -- and its last
+ * row increments *t (int32, 1-based token index).  The parameters are read from DEVICE memory, so a captured launch serves
+ * any configuration.  Limits: 1 <= B <= 1024, 1 <= V <= 2^20 (else AWQ_ERR_UNSUPPORTED).  workspace: 256-byte aligned,
+ * awq_sample_workspace_bytes(B, V) bytes, zeroed ONCE by the caller; every call leaves it zero again.  One workspace serves
+ * one stream at a time.  AWQ_SAMPLE_FLAG_GREEDY: greedy whatever the parameters say, one launch instead of three. */
+typedef struct AwqSampleParams {
+    uint64_t seed;
+    int32_t do_sample;
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    int32_t n_eos;   /* 0 .. 8 */
+    int32_t pad;     /* the token of finished and failed rows */
+    int32_t eos[8];
+} AwqSampleParams;
+
+#define AWQ_SAMPLE_FLAG_GREEDY 1u
+
+typedef struct AwqSampleArgs {
+    uint32_t struct_bytes; /* sizeof(AwqSampleArgs) */
+    uint32_t flags;
+    const uint16_t* logits;
+    int64_t B;
+    int64_t V;
+    int64_t row_stride;    /* elements */
+    const AwqSampleParams* params;
+    int32_t* t;
+    int64_t* out;
+    int64_t out_stride;    /* elements */
+    int32_t* ring;         /* [B, ring_cap] or NULL */
+    int64_t ring_cap;
+    int32_t* finished;     /* [B] or NULL */
+    uint32_t* status;      /* [ceil(B / 32)] */
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+} AwqSampleArgs;
+
+AWQ_EXPORT size_t awq_sample_workspace_bytes(int64_t B, int64_t V);
+AWQ_EXPORT int awq_sample_tokens(const AwqSampleArgs* args);
+
 #ifdef __cplusplus
 }
 #endif

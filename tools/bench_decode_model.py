@@ -13,11 +13,9 @@ sys.path.insert(0, ROOT)
 H, I, V, HEADS, G = 4096, 11008, 32000, 32, 128
 
 
-def run(layers=32, contexts=(64, 512, 2048), batch=1, steps=64, dev=None, verbose=True, check=True, layout="gemm",
-        hidden=H, inter=I, vocab=V, heads=HEADS):
-    """Returns {context: ms_per_token}.  check: before timing, the logits of the five-launch stream path (norms folded
-    into the projections, fused RoPE + append + attention) must agree with the plain module path (separate norm, RoPE /
-    append, attention, o_proj, MLP launches) on the same weights and cache."""
+def build_model(layers, max_ctx, dev, layout="gemm", hidden=H, inter=I, vocab=V, heads=HEADS):
+    """The synthetic fused model: random int4 layers of the given shape, a cache window of max_ctx rows.
+    Returns (lm, blocks, generator)."""
     from autoawq_amd.fuser import FusedCausalLM
     from autoawq_amd.modules.fused.block import LlamaLikeBlock
     from autoawq_amd.modules.fused.mlp import QuantFusedMLP
@@ -25,7 +23,6 @@ def run(layers=32, contexts=(64, 512, 2048), batch=1, steps=64, dev=None, verbos
     from autoawq_amd.modules.fused.norm import FasterTransformerRMSNorm
     from autoawq_amd.modules.linear import WQLinear_GEMM
 
-    dev = dev or torch.device("cuda")
     gen = torch.Generator(device=dev).manual_seed(0)
     lim = 0x7FFFFFFF
     H, I, V, HEADS = hidden, inter, vocab, heads  # (tests run a small stack through the same code)
@@ -47,7 +44,6 @@ def run(layers=32, contexts=(64, 512, 2048), batch=1, steps=64, dev=None, verbos
         m.scales = (torch.rand((K // G, N), device=dev, generator=gen) * 0.004 + 0.001).half()
         return m
 
-    max_ctx = max(contexts) + steps + 8
     ones = lambda: torch.ones(H, dtype=torch.float16, device=dev)
     blocks = []
     for _ in range(layers):
@@ -57,6 +53,19 @@ def run(layers=32, contexts=(64, 512, 2048), batch=1, steps=64, dev=None, verbos
     emb = nn.Embedding(V, H).half().to(dev)
     head = nn.Linear(H, V, bias=False).half().to(dev)
     lm = FusedCausalLM(LlamaLikeModel(V, blocks, emb, FasterTransformerRMSNorm(ones(), 1e-5)), head)
+    return lm, blocks, gen
+
+
+def run(layers=32, contexts=(64, 512, 2048), batch=1, steps=64, dev=None, verbose=True, check=True, layout="gemm",
+        hidden=H, inter=I, vocab=V, heads=HEADS):
+    """Returns {context: ms_per_token}.  check: before timing, the logits of the five-launch stream path (norms folded
+    into the projections, fused RoPE + append + attention) must agree with the plain module path (separate norm, RoPE /
+    append, attention, o_proj, MLP launches) on the same weights and cache."""
+    from autoawq_amd.modules.fused.block import LlamaLikeBlock
+
+    dev = dev or torch.device("cuda")
+    H, I, V, HEADS = hidden, inter, vocab, heads  # (tests run a small stack through the same code)
+    lm, blocks, gen = build_model(layers, max(contexts) + steps + 8, dev, layout, hidden, inter, vocab, heads)
     from autoawq_amd.modules.fused.decode import GraphedDecoder
 
     dec = GraphedDecoder(lm, batch=batch)  # one hipGraph per length bucket (256 / 1024 / 4096 ... rows); positions on the device

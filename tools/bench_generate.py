@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Token generation on the synthetic Llama-2-7B-shape model of tools/bench_decode_model.py: GraphedDecoder.generate (the
+sampler captured into the decode graph, the host looking at the flags every 16 tokens) against the loop users write by hand
+(dec.step + torch.argmax + a per-token .item() EOS check), at several contexts and batch sizes.  Decode tok/s excludes the
+prompt's prefill (timed on its own and subtracted).  --sampler-only times the sampler alone (run it under
+`rocprofv3 --kernel-trace --stats` for per-kernel durations)."""
+import argparse, json, os, sys, time
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, r
+
+
+def bench_generate(layers=32, contexts=(64, 2048), batches=(1, 4), new=128):
+    import bench_decode_model
+    from autoawq_amd.modules.fused.decode import GraphedDecoder
+
+    dev = torch.device("cuda")
+    lm, blocks, gen = bench_decode_model.build_model(layers, max(contexts) + new + 8, dev, layout="gemv")
+    V = bench_decode_model.V
+    rows = []
+    for B in batches:
+        dec = GraphedDecoder(lm, batch=B)
+        for ctx in contexts:
+            prompt = torch.randint(0, V, (B, ctx), device=dev, generator=gen)
+            dec.prefill(prompt)  # warm-up (lazy buffers)
+            t_pre = min(_timed(lambda: dec.prefill(prompt))[0] for _ in range(2))
+
+            def hand():
+                logits = dec.prefill(prompt)
+                for _ in range(new - 1):
+                    tok = torch.argmax(logits[:, -1], -1)
+                    if (tok == -1).any().item():  # the EOS check: a host round trip per token
+                        break
+                    logits = dec.step(tok)
+                return torch.argmax(logits[:, -1], -1)
+
+            cfgs = [("hand greedy", hand), ("generate greedy", lambda: dec.generate(prompt, new)),
+                    ("generate top_k=50 top_p=0.9", lambda: dec.generate(prompt, new, do_sample=True, top_k=50, top_p=0.9, seed=1))]
+            for name, fn in cfgs:
+                fn()  # captures
+                t = min(_timed(fn)[0] for _ in range(2))
+                dt = max(t - t_pre, 1e-9)
+                r = {"batch": B, "context": ctx, "mode": name, "new_tokens": new, "total_s": round(t, 5), "prefill_s": round(t_pre, 5),
+                     "decode_tok_s": round(B * (new - 1) / dt, 1)}
+                rows.append(r)
+                print(json.dumps(r), flush=True)
+        del dec
+    return rows
+
+
+def bench_sampler(vocabs=(32000, 128256, 152064), batches=(1, 4), calls=200):
+    from autoawq_amd import ops
+
+    dev = torch.device("cuda")
+    rows = []
+    for V in vocabs:
+        for B in batches:
+            x = (torch.randn((B, V), device=dev) * 3).half()
+            t = torch.ones(1, dtype=torch.int32, device=dev)
+            out = torch.empty(B, dtype=torch.int64, device=dev)
+            status = torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev)
+            ws = torch.zeros(ops.sample_workspace_bytes(B, V), dtype=torch.uint8, device=dev)
+            for name, greedy, cfg in (("greedy", True, {"do_sample": False}),
+                                      ("top_k=50 top_p=0.9", False, {"do_sample": True, "top_k": 50, "top_p": 0.9, "seed": 1}),
+                                      ("top_p=0.9", False, {"do_sample": True, "top_p": 0.9, "seed": 1})):
+                params = ops.sample_params(**cfg).to(dev)
+                launch = lambda: ops.sample_launch(x, params, t, out, status, ws, greedy=greedy)
+                s = torch.cuda.Stream()
+                with torch.cuda.stream(s):
+                    launch()
+                    s.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, stream=s):
+                        for _ in range(10):
+                            launch()
+                    g.replay()
+                    s.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(s)
+                    for _ in range(calls // 10):
+                        g.replay()
+                    e1.record(s)
+                    e1.synchronize()
+                us = e0.elapsed_time(e1) * 1000.0 / calls
+                assert int(status.count_nonzero()) == 0 and int(ws.count_nonzero()) == 0
+                r = {"V": V, "batch": B, "mode": name, "us_per_call_in_graph": round(us, 2)}
+                rows.append(r)
+                print(json.dumps(r), flush=True)
+    return rows
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sampler-only", action="store_true")
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--new", type=int, default=128)
+    a = ap.parse_args()
+    if a.sampler_only:
+        bench_sampler()
+    else:
+        bench_generate(layers=a.layers, new=a.new)
