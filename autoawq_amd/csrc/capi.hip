@@ -643,6 +643,17 @@ int awq_rope_kv_append(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, 
                                      static_cast<hipStream_t>(stream));
 }
 
+int awq_rope_kv_append_rows(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, const float* cos_table,
+                            const float* sin_table, const int32_t* pos_rows, int64_t B, int64_t S, int64_t n_heads,
+                            int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim, int64_t max_seq, void* stream) {
+    if (B < 0 || S < 0 || B * S > INT32_MAX / 1024 || max_seq < 1 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (B * S == 0) return AWQ_OK;
+    if (!qkv || !q_out || !k_cache || !v_cache || !pos_rows || (rotary_dim > 0 && (!cos_table || !sin_table))) return AWQ_ERR_NULL;
+    return awq_launch_rope_kv_append(qkv, q_out, k_cache, v_cache, cos_table, sin_table, pos_rows, 0, (int)B, (int)S,
+                                     (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)rotary_dim, (int)max_seq,
+                                     static_cast<hipStream_t>(stream), true);
+}
+
 size_t awq_decode_attention_workspace_bytes(int64_t B, int64_t n_heads) {
     if (B <= 0 || n_heads <= 0) return 0;
     return awq_decode_attention_workspace_bytes_impl((int)B, (int)n_heads, 64);
@@ -689,4 +700,32 @@ int awq_decode_attention_rope(const uint16_t* qkv, uint16_t* k_cache, uint16_t* 
     return awq_launch_decode_attention(qkv, k_cache, v_cache, out, pos_dev, (int)start_pos, (int)max_len, (int)B, (int)n_heads,
                                        (int)n_kv_heads, (int)head_dim, (int)max_seq, scale, workspace, workspace_bytes,
                                        cos_table, sin_table, static_cast<hipStream_t>(stream));
+}
+
+int awq_decode_attention_rows(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
+                              const int32_t* len_rows, int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads,
+                              int64_t head_dim, int64_t max_seq, float scale, float softcap, const float* alibi_slopes,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (!(softcap >= 0.f)) return AWQ_ERR_BAD_SHAPE;
+    if (B == 0) return AWQ_OK;
+    if (!q || !k_cache || !v_cache || !out || !len_rows) return AWQ_ERR_NULL;
+    if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
+    return awq_launch_decode_attention(q, const_cast<uint16_t*>(k_cache), const_cast<uint16_t*>(v_cache), out, len_rows, 1,
+                                       (int)max_len, (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_seq, scale,
+                                       workspace, workspace_bytes, nullptr, nullptr, static_cast<hipStream_t>(stream), softcap,
+                                       alibi_slopes, true);
+}
+
+int awq_decode_attention_rope_rows(const uint16_t* qkv, uint16_t* k_cache, uint16_t* v_cache, const float* cos_table,
+                                   const float* sin_table, uint16_t* out, const int32_t* pos_rows, int64_t max_len, int64_t B,
+                                   int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (B == 0) return AWQ_OK;
+    if (!qkv || !k_cache || !v_cache || !out || !cos_table || !sin_table || !pos_rows) return AWQ_ERR_NULL;
+    if (!aligned16(qkv) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
+    return awq_launch_decode_attention(qkv, k_cache, v_cache, out, pos_rows, 0, (int)max_len, (int)B, (int)n_heads,
+                                       (int)n_kv_heads, (int)head_dim, (int)max_seq, scale, workspace, workspace_bytes,
+                                       cos_table, sin_table, static_cast<hipStream_t>(stream), 0.f, nullptr, true);
 }

@@ -99,6 +99,9 @@ __global__ __launch_bounds__(256) void awq_rmsnorm_kernel(const half_t* __restri
 // (i, i + rot/2) of a q or k head by the angle of position start + s (cos/sin tables
 // [max_pos, rot/2] fp32, built like RoPE.precompute_freqs_cis), passes dims >= rot through, and
 // writes q to q_out [B*S, Hq, D], k / v to the caches [B, Tmax, Hkv, D] at row start + s.
+// ROWS (awq_rope_kv_append_rows): every sequence b has its own start, pos_dev[b] ([B] int32 on the device, never NULL) --
+// batches of prompts of different lengths (modules/fused/decode.py); clamped to [0, Tmax - 1] like the shared one.
+template <bool ROWS = false>
 __global__ __launch_bounds__(128) void awq_rope_kv_append_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ q_out,
                                                                 half_t* __restrict__ k_cache, half_t* __restrict__ v_cache,
                                                                 const float* __restrict__ cos_t, const float* __restrict__ sin_t,
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(128) void awq_rope_kv_append_kernel(const half_t* _
     // A device-side position (hipGraph replay) is not seen by the host checks: clamp it to the cache so that a
     // replay past max_seq_len overwrites the last row instead of memory behind the cache / the cos-sin tables
     // (the caller is expected to roll the window before that: modules/fused/model.py).
-    const int pos = min((pos_dev ? *pos_dev : start_pos) + s, Tmax - 1);
+    const int pos = ROWS ? max(0, min(pos_dev[b] + s, Tmax - 1)) : min((pos_dev ? *pos_dev : start_pos) + s, Tmax - 1);
     const int i = threadIdx.x;  // 0 .. D/2-1
     const half_t* src = qkv + (int64_t)tok * (Hq + 2 * Hkv) * D + (int64_t)slot * D;
     half_t* dst;
@@ -151,7 +154,10 @@ __global__ __launch_bounds__(128) void awq_rope_kv_append_kernel(const half_t* _
 // kernel: rotated values pass through fp16.
 // EXTRA (plain form only): logit soft-capping s := cap * tanh(s / cap) (attn.py:150,166 `softcap=`) and ALiBi, a per-head linear
 // bias slope_h * (t - pos) on the key position (attn.py:89-125,149,165 `alibi_slopes=`), in that order like flash-attn.
-template <int G, bool FUSED, bool EXTRA = false>
+// ROWS (the *_rows entry points): len_dev is [B], sequence b reads its own length (FUSED: position) from len_dev[b].  The launch
+// is still sized on the host for the bucket's bound; a block deals the rows of ITS sequence to the splits, so a short sequence in
+// a long bucket leaves the last splits empty -- they write the (-inf, 0) partial the combine kernel gives weight 0.
+template <int G, bool FUSED, bool EXTRA = false, bool ROWS = false>
 __global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __restrict__ q, half_t* __restrict__ kc,
                                                              half_t* __restrict__ vc, half_t* __restrict__ out,
                                                              float* __restrict__ part, const int* __restrict__ len_dev,
@@ -189,7 +195,7 @@ __global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __re
         }
     }
     // device-side lengths are clamped to the cache (see awq_rope_kv_append_kernel): never a row >= Tmax
-    const int T = max(1, min((len_dev ? *len_dev : seq_len) + (FUSED ? 1 : 0), Tmax));
+    const int T = max(1, min((ROWS ? len_dev[b] : (len_dev ? *len_dev : seq_len)) + (FUSED ? 1 : 0), Tmax));
     const int pos = T - 1;  // FUSED: the new token's position
     // The rows are dealt to the splits of the launch HERE, from the length the device knows (round 4): a launch sized on the host
     // for a longer context (a hipGraph serves every length up to its bucket's bound) still spreads the rows that exist over
@@ -392,14 +398,15 @@ int awq_launch_rmsnorm(const uint16_t* x, uint16_t* residual, const uint16_t* w,
 
 int awq_launch_rope_kv_append(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, const float* cos_t,
                               const float* sin_t, const int32_t* pos_dev, int start_pos, int B, int S, int Hq, int Hkv, int D,
-                              int rot, int Tmax, hipStream_t st) {
+                              int rot, int Tmax, hipStream_t st, bool rows) {
     if (B < 0 || S < 0 || Hq < 1 || Hkv < 1 || D < 2 || D % 2 || D > 256 || rot < 0 || rot > D || rot % 2)
         return AWQ_ERR_BAD_SHAPE;
+    if (rows && !pos_dev) return AWQ_ERR_NULL;
     if (!pos_dev && (start_pos < 0 || start_pos + S > Tmax)) return AWQ_ERR_BAD_SHAPE;
     if (B * S == 0) return AWQ_OK;
     const unsigned blocks = (unsigned)((int64_t)B * S * (Hq + 2 * Hkv));
-    hipLaunchKernelGGL(awq_rope_kv_append_kernel, dim3(blocks), dim3(D / 2), 0, st, reinterpret_cast<const half_t*>(qkv),
-                       reinterpret_cast<half_t*>(q_out), reinterpret_cast<half_t*>(k_cache),
+    hipLaunchKernelGGL(rows ? awq_rope_kv_append_kernel<true> : awq_rope_kv_append_kernel<false>, dim3(blocks), dim3(D / 2), 0, st,
+                       reinterpret_cast<const half_t*>(qkv), reinterpret_cast<half_t*>(q_out), reinterpret_cast<half_t*>(k_cache),
                        reinterpret_cast<half_t*>(v_cache), cos_t, sin_t, pos_dev, start_pos, S, Hq, Hkv, D, rot, Tmax);
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
@@ -408,21 +415,22 @@ size_t awq_decode_attention_workspace_bytes_impl(int B, int Hq, int max_splits) 
     return (size_t)B * Hq * max_splits * (128 + 2) * sizeof(float);
 }
 
-template <int G, bool FUSED, bool EXTRA = false>
+template <int G, bool FUSED, bool EXTRA = false, bool ROWS = false>
 static void launch_attn(dim3 grid, hipStream_t st, const uint16_t* q, uint16_t* kc, uint16_t* vc, uint16_t* out, float* part,
                         const int32_t* len_dev, int seq_len, int Hq, int Hkv, int Tmax, float scale, int chunk,
                         const float* cos_t, const float* sin_t, float softcap = 0.f, const float* alibi = nullptr) {
-    hipLaunchKernelGGL((awq_decode_attn_kernel<G, FUSED, EXTRA>), grid, dim3(256), 0, st, reinterpret_cast<const half_t*>(q),
+    hipLaunchKernelGGL((awq_decode_attn_kernel<G, FUSED, EXTRA, ROWS>), grid, dim3(256), 0, st, reinterpret_cast<const half_t*>(q),
                        reinterpret_cast<half_t*>(kc), reinterpret_cast<half_t*>(vc), reinterpret_cast<half_t*>(out), part,
                        len_dev, seq_len, Hq, Hkv, Tmax, scale, chunk, cos_t, sin_t, softcap, alibi);
 }
 
 // cos_t == nullptr: plain form (q [B, Hq, D], rows [0, len) of the caches).  Otherwise the fused form:
-// q = raw qkv rows, `len_dev` / `seq_len` carry the POSITION of the new token.
+// q = raw qkv rows, `len_dev` / `seq_len` carry the POSITION of the new token.  rows: len_dev is [B], one word per sequence.
 int awq_launch_decode_attention(const uint16_t* q, uint16_t* k_cache, uint16_t* v_cache, uint16_t* out,
                                 const int32_t* len_dev, int seq_len, int max_len, int B, int Hq, int Hkv, int D, int Tmax,
                                 float scale, void* workspace, size_t workspace_bytes, const float* cos_t,
-                                const float* sin_t, hipStream_t st, float softcap, const float* alibi) {
+                                const float* sin_t, hipStream_t st, float softcap, const float* alibi, bool rows) {
+    if (rows && !len_dev) return AWQ_ERR_NULL;
     if (D != 128) return AWQ_ERR_UNSUPPORTED;
     const bool extra = softcap > 0.f || alibi != nullptr;
     if (extra && cos_t) return AWQ_ERR_UNSUPPORTED;  // ALiBi models do not rotate; soft-capping takes the two-launch form
@@ -466,7 +474,14 @@ int awq_launch_decode_attention(const uint16_t* q, uint16_t* k_cache, uint16_t* 
     float* part = static_cast<float*>(workspace);
 #define AWQ_ATTN_CASE(GG)                                                                                                  \
     case GG:                                                                                                               \
-        if (extra) launch_attn<GG, false, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, \
+        if (rows) {                                                                                                        \
+            if (extra) launch_attn<GG, false, true, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, \
+                                                          Tmax, scale, chunk, nullptr, nullptr, softcap, alibi);           \
+            else if (fused) launch_attn<GG, true, false, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, \
+                                                               Hkv, Tmax, scale, chunk, cos_t, sin_t);                     \
+            else launch_attn<GG, false, false, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, \
+                                                     scale, chunk, nullptr, nullptr);                                      \
+        } else if (extra) launch_attn<GG, false, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, \
                                                 scale, chunk, nullptr, nullptr, softcap, alibi);                            \
         else if (fused) launch_attn<GG, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, scale, \
                                          chunk, cos_t, sin_t);                                                             \

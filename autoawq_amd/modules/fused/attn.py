@@ -12,7 +12,8 @@ MI355X-first differences:
     torch's scaled_dot_product_attention, where the reference calls flash_attn_func (:277-285):
     vendor attention is plumbing here, the int4 projections are the product;
   * `use_device_positions(pos, length)`: start position and length live in device int32 tensors so
-    that one captured hipGraph can be replayed for every decode step.
+    that one captured hipGraph can be replayed for every decode step; with `per_row=True` they hold one word per sequence
+    (batches of prompts of different lengths) and the decode steps call the *_rows forms of the kernels.
   * the feature surface of attn.py:89-125,159-203 rides on the same kernels: `attention_shapes` (how the fused row is viewed and
     sliced, awq/utils/fused_utils.py:165-201) and `q_norm` / `k_norm` are applied to the projection's output, which is then put
     back into the q | k | v head order the kernels read; ALiBi models skip the rotation (rotary width 0 in the append kernel)
@@ -117,11 +118,15 @@ class QuantAttentionFused(nn.Module):
             self.is_neox = True
         self._pos_dev = None
         self._len_dev = None
+        self._per_row = False
 
-    def use_device_positions(self, pos_dev, len_dev):
+    def use_device_positions(self, pos_dev, len_dev, per_row=False):
         """pos_dev / len_dev: int32 device tensors of one element (shared by all layers) holding the
-        start position and the cache length after the append; the caller advances them."""
-        self._pos_dev, self._len_dev = pos_dev, len_dev
+        start position and the cache length after the append; the caller advances them.  per_row=True: both are [B], one
+        position and one length per sequence (decode steps only; the host-side start_pos of prefill is not per row)."""
+        if per_row and (pos_dev is None or len_dev is None):
+            raise ValueError("use_device_positions: per_row needs both the position and the length words")
+        self._pos_dev, self._len_dev, self._per_row = pos_dev, len_dev, bool(per_row)
 
     def _len_bound(self):
         """What a decode launch with a DEVICE-side length is sized for: the cache window, or the tighter bound a caller that
@@ -186,6 +191,7 @@ class QuantAttentionFused(nn.Module):
         self._resize_cache(bsz)
         xqkv = self._qkv_rows(xqkv)
         device_pos = self._pos_dev is not None and seqlen == 1
+        rows = device_pos and self._per_row  # one position / length word per sequence: the *_rows kernels
         # the hand-written decode kernels take head_dim 128 and 1, 2, 4 or 8 query heads per KV head; other
         # shapes (e.g. 24 / 8 heads, 28 / 4) take the vendor path below instead of failing at the first decode step
         native = self.head_dim == 128 and self.n_kv_groups in (1, 2, 4, 8)
@@ -193,15 +199,18 @@ class QuantAttentionFused(nn.Module):
         if seqlen == 1 and native and self.rotary_dim == 128 and self.FUSE_ROPE_INTO_ATTENTION and not modified:
             # decode: rotation, cache append and attention in ONE launch (awq_decode_attention_rope)
             out = ops.decode_attention_rope(xqkv, self.cache.k, self.cache.v, self.rope.cos, self.rope.sin, self.start_pos,
-                                            self.n_heads, self.n_kv_heads, pos_dev=self._pos_dev if device_pos else None,
-                                            max_len=self._len_bound() if device_pos else None)
+                                            self.n_heads, self.n_kv_heads,
+                                            pos_dev=self._pos_dev if device_pos and not rows else None,
+                                            max_len=self._len_bound() if device_pos else None,
+                                            pos_rows=self._pos_dev if rows else None)
             attention_weight = out.reshape(bsz, 1, -1)
             attn_output = self.o_proj(attention_weight) if apply_o_proj else attention_weight
             self.start_pos += 1
             return attn_output, attention_weight, [torch.zeros(1, 1, self.start_pos, 1)]
         xq = ops.rope_kv_append(xqkv, self.cache.k, self.cache.v, self.rope.cos, self.rope.sin, self.start_pos,
                                 self.n_heads, self.n_kv_heads, self.head_dim, self.rotary_dim,
-                                pos_dev=self._pos_dev if device_pos else None)
+                                pos_dev=self._pos_dev if device_pos and not rows else None,
+                                pos_rows=self._pos_dev if rows else None)
         if seqlen > 1 and self.head_dim == 128 and self.n_heads % self.n_kv_heads == 0 and self.PREFILL_KERNEL:
             # prefill: the hand-written flash-style kernel (csrc/prefill_attn.hip; the reference's flash_attn_func call, attn.py:269-277),
             # chunked prefill, GQA, ALiBi and the soft cap included -- no mask tensor, no repeat_interleave copy of the cache
@@ -226,6 +235,9 @@ class QuantAttentionFused(nn.Module):
             output = out.transpose(1, 2).reshape(bsz, seqlen, -1)
         else:
             if not native:  # the hand-written kernel is specialised (head_dim, GQA ratio); other shapes take the vendor path
+                if rows:
+                    raise NotImplementedError("per-row decode positions need the native decode attention (head_dim 128, "
+                                              "1, 2, 4 or 8 query heads per KV head)")
                 k = self.cache.k[:bsz, : self.start_pos + 1].transpose(1, 2)
                 v = self.cache.v[:bsz, : self.start_pos + 1].transpose(1, 2)
                 if self.n_kv_groups > 1:
@@ -237,9 +249,10 @@ class QuantAttentionFused(nn.Module):
                     output = F.scaled_dot_product_attention(xq.transpose(1, 2), k, v).transpose(1, 2).reshape(bsz, 1, -1)
             else:
                 out = ops.decode_attention(xq[:, 0], self.cache.k, self.cache.v, self.start_pos + 1,
-                                           len_dev=self._len_dev if device_pos else None, max_len=self._len_bound(),
+                                           len_dev=self._len_dev if device_pos and not rows else None, max_len=self._len_bound(),
                                            softcap=self.attn_logit_softcapping,
-                                           alibi_slopes=self.alibi.slopes if self.alibi is not None else None)
+                                           alibi_slopes=self.alibi.slopes if self.alibi is not None else None,
+                                           len_rows=self._len_dev if rows else None)
                 output = out.reshape(bsz, 1, -1)
         attention_weight = output
         attn_output = self.o_proj(attention_weight) if apply_o_proj else attention_weight

@@ -50,6 +50,18 @@ class WindowedCache:
             self.kv[:, :, :live].copy_(moved)
         return live
 
+    def roll_rows(self, rows, n):
+        """Forget the n oldest positions of the sequences `rows` only (the other sequences keep their contents): cache rows
+        n .. max_seq_len - 1 of each move to 0 .. max_seq_len - n - 1.  The per-sequence form of roll_kv_n_steps for batches
+        whose sequences have their own lengths (modules/fused/decode.py); the caller lowers those sequences' positions by n."""
+        n = max(0, min(int(n), self.max_seq_len))
+        rows = [int(r) for r in rows]
+        if not n or not rows or n == self.max_seq_len:
+            return
+        idx = torch.tensor(rows, dtype=torch.long, device=self.kv.device)
+        moved = self.kv[:, idx, n:].clone()  # [2, len(rows), max_seq_len - n, heads, head_dim]
+        self.kv[:, idx, : self.max_seq_len - n] = moved
+
     def to(self, device):
         self._alloc(self.kv.shape[1], self.kv.shape[3], self.kv.shape[4], device, keep=self.kv)
 

@@ -26,12 +26,21 @@ the next ids straight into the step's input buffer, a ring of generated tokens a
 picks buckets, rolls the window and looks at the flags every `check_every` tokens.
 
     out = dec.generate(prompt_ids, max_new_tokens=64, do_sample=True, top_p=0.9, seed=1)   # [batch, prompt + n] int64
+
+Prompts of different lengths come as one padded batch with an `attention_mask` (transformers' convention; modules/fused/
+ragged.py).  Every row then has its own position: `pos_rows` / `len_rows` hold one word per row, a second family of graphs
+(`row_graphs`, `row_gen_graphs`) reads them through the *_rows kernels, the host keeps one position per row (`positions`),
+picks the bucket from the largest and rolls a row's window on its own when that row alone would run past it.  No mask, or
+an all-ones mask, takes the shared words and the graphs above unchanged.
+
+    out = dec.generate(ids, attention_mask=mask, max_new_tokens=64)   # left-padded ids: transformers' layout
 """
 import torch
 
 from ... import ops
 from ..._lib import AwqHipError
 from .model import StepPlan
+from .ragged import mask_runs, pack_ids, unpack_rows
 
 
 class GraphedDecoder:
@@ -64,16 +73,25 @@ class GraphedDecoder:
             self.pos = torch.zeros(1, dtype=torch.int32, device=self.device)   # start position of the step
             self.len = torch.ones(1, dtype=torch.int32, device=self.device)    # cache rows after its append
             self.tok = torch.zeros((self.batch, 1), dtype=torch.int64, device=self.device)
+            self.pos_rows = torch.zeros(self.batch, dtype=torch.int32, device=self.device)  # per-row mode: start position of
+            self.len_rows = torch.ones(self.batch, dtype=torch.int32, device=self.device)   # each row, its cache rows after the append
         self.stream = torch.cuda.Stream(device=self.device)
         self.graphs = {}  # bucket bound -> (graph, logits)
         self.gen_graphs = {}  # (bucket bound, greedy) -> (graph, logits): step + sampler (generate)
+        self.row_graphs = {}  # per-row mode (attention_mask): bucket bound -> (graph, logits), reading pos_rows / len_rows
+        self.row_gen_graphs = {}  # per-row mode: (bucket bound, greedy) -> (graph, logits)
         self._gen = None  # generate's device words (allocated by its first call)
         self.position = 0
+        self.positions = None  # per-row mode: the host's position of every row (None: one shared position)
         for b in self.blocks:
             b.attn._resize_cache(self.batch)
 
     # ---- bookkeeping ------------------------------------------------------------------------------------------------
     def _sync_host_state(self):
+        # (per-row mode: the largest position -- the host-side bookkeeping of the blocks then never rolls the shared window,
+        #  the rows that would run past it have been rolled one by one before)
+        if self.positions is not None:
+            self.position = max(self.positions)
         for b in self.blocks:
             b.attn.start_pos = self.position
         self.lm.model.last_forward_num_tokens = self.position
@@ -82,9 +100,23 @@ class GraphedDecoder:
         """Declare that `position` cache rows are valid (benchmarks and tests that fill the caches themselves)."""
         if not 0 <= position <= self.max_seq_len:  # (== max_seq_len: a full window -- the next step rolls it first)
             raise ValueError(f"position {position} outside the cache window {self.max_seq_len}")
+        self.positions = None
         self.position = int(position)
         self.pos.fill_(self.position)
         self.len.fill_(self.position + 1)
+        self._sync_host_state()
+
+    def seek_rows(self, positions):
+        """Per-row mode: declare that row b has positions[b] valid cache rows.  Later steps use the per-row graphs."""
+        positions = [int(p) for p in positions]
+        if len(positions) != self.batch:
+            raise ValueError(f"seek_rows: {len(positions)} positions for a batch of {self.batch}")
+        if not all(0 <= p <= self.max_seq_len for p in positions):
+            raise ValueError(f"seek_rows: positions {positions} outside the cache window {self.max_seq_len}")
+        self.positions = positions
+        p = torch.tensor(positions, dtype=torch.int32)
+        self.pos_rows.copy_(p)
+        self.len_rows.copy_(p + 1)
         self._sync_host_state()
 
     def bucket(self, rows):
@@ -94,23 +126,49 @@ class GraphedDecoder:
         return self.bounds[-1]
 
     # ---- prefill: eager (any number of tokens; the reference's own path) ----------------------------------------------
-    @torch.inference_mode()
-    def prefill(self, input_ids):
+    def _ragged(self, input_ids, attention_mask):
+        """(starts, lengths) of the mask's runs, or None when there is no mask or every row is full (the shared path)"""
+        if attention_mask is None:
+            return None
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
+            raise ValueError(f"input_ids must be [{self.batch}, prompt] with an attention_mask, got {tuple(input_ids.shape)}")
+        starts, lengths = mask_runs(attention_mask, input_ids.shape, max_len=self.max_seq_len)
+        if all(n == input_ids.shape[1] for n in lengths):
+            return None
+        return starts, lengths
+
+    def _prefill_eager(self, input_ids):
         for b in self.blocks:
             b.attn.use_device_positions(None, None)
             b.attn.start_pos = 0
         self.lm.model.last_forward_num_tokens = 0
-        logits = self.lm(input_ids.to(self.device))
-        self.seek(self.blocks[0].attn.start_pos)
-        return logits
+        return self.lm(input_ids.to(self.device))
+
+    @torch.inference_mode()
+    def prefill(self, input_ids, attention_mask=None):
+        """input_ids [B, S] -> logits [B, S, vocab], eager.  attention_mask [B, S] of 0 / 1 (transformers' convention, each row's
+        ones one contiguous run: left or right padding): row b's L_b real tokens get positions 0 .. L_b - 1 and the decoder
+        switches to per-row positions.  The logits come back in the caller's layout; the values at pad columns are
+        unspecified.  No mask, or an all-ones mask, is exactly the unmasked call."""
+        input_ids = input_ids.to(self.device)
+        ragged = self._ragged(input_ids, attention_mask)
+        if ragged is None:
+            logits = self._prefill_eager(input_ids)
+            self.seek(self.blocks[0].attn.start_pos)
+            return logits
+        starts, lengths = ragged
+        logits = self._prefill_eager(pack_ids(input_ids, starts, lengths))  # [B, max L_b, V]: row b's tokens at 0 .. L_b - 1
+        self.seek_rows(lengths)
+        return unpack_rows(logits, starts, lengths, input_ids.shape[1])
 
     # ---- one token ------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
-    def _capture(self, bound, sample=None):
+    def _capture(self, bound, sample=None, rows=False):
+        pos, ln = (self.pos_rows, self.len_rows) if rows else (self.pos, self.len)
         for b in self.blocks:
-            b.attn.use_device_positions(self.pos, self.len)
+            b.attn.use_device_positions(pos, ln, per_row=rows)
             b.attn.decode_len_bound = bound
-        keep = (self.pos.clone(), self.len.clone())
+        keep = (pos.clone(), ln.clone())
         caller = torch.cuda.current_stream(self.device)  # (taken BEFORE entering the decoder's stream: the ids were copied on it)
         with torch.cuda.stream(self.stream):
             self.stream.wait_stream(caller)
@@ -124,22 +182,38 @@ class GraphedDecoder:
                 logits = self.lm(self.tok)
                 if sample is not None:
                     sample(logits)
-                self.pos.add_(1)
-                self.len.add_(1)
+                pos.add_(1)
+                ln.add_(1)
             self.stream.synchronize()
-            self.pos.copy_(keep[0])
-            self.len.copy_(keep[1])
+            pos.copy_(keep[0])
+            ln.copy_(keep[1])
         caller.wait_stream(self.stream)
         self._sync_host_state()
         if sample is not None:
             return graph, logits
-        self.graphs[bound] = (graph, logits)
-        return self.graphs[bound]
+        graphs = self.row_graphs if rows else self.graphs
+        graphs[bound] = (graph, logits)
+        return graphs[bound]
+
+    def _roll_rows(self):
+        """Per-row mode: every row that alone would run past the window forgets its oldest StepPlan.ROLL positions, as
+        roll_kv_n_steps does for a row decoded alone; the other rows keep their contents."""
+        over = [r for r, p in enumerate(self.positions) if p + 1 > self.max_seq_len]
+        if not over:
+            return
+        for r in over:
+            n = max(0, min(StepPlan.ROLL, self.positions[r], self.max_seq_len))
+            for b in self.blocks:
+                b.attn.cache.roll_rows([r], n)
+            self.positions[r] -= n
+        self.seek_rows(self.positions)
 
     def _advance(self, greedy=None):
         """What `step` and `replay` share: roll a full window, pick (or capture) the bucket's graph, replay it on the decoder's stream
         between the caller's work, advance the position on the host as the graph did on the device.  greedy = True / False:
         the generation graph (step + sampler) instead of the step graph."""
+        if self.positions is not None:
+            return self._advance_rows(greedy)
         if self.position + 1 > self.max_seq_len:  # past the window: forget the oldest positions (eagerly)
             live = [b.attn.cache.roll_kv_n_steps(self.position, n=StepPlan.ROLL) for b in self.blocks][0]
             self.seek(live)
@@ -157,6 +231,26 @@ class GraphedDecoder:
             graph.replay()
         caller.wait_stream(self.stream)   # ... and the caller reads the logits
         self.position += 1
+        self._sync_host_state()
+        return logits
+
+    def _advance_rows(self, greedy=None):
+        """`_advance` in per-row mode: per-row rolls, the bucket of the largest position, the per-row graphs."""
+        self._roll_rows()
+        bound = self.bucket(max(self.positions) + 1)
+        if greedy is None:
+            graph, logits = self.row_graphs.get(bound) or self._capture(bound, rows=True)
+        else:
+            key = (bound, bool(greedy))
+            if key not in self.row_gen_graphs:
+                self.row_gen_graphs[key] = self._capture(bound, sample=lambda lg: self._sample(lg, greedy), rows=True)
+            graph, logits = self.row_gen_graphs[key]
+        caller = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            graph.replay()
+        caller.wait_stream(self.stream)
+        self.positions = [p + 1 for p in self.positions]
         self._sync_host_state()
         return logits
 
@@ -190,6 +284,7 @@ class GraphedDecoder:
                  "status": torch.zeros((self.batch + 31) // 32, dtype=torch.int32, device=dev),
                  "ws": torch.zeros(ops.sample_workspace_bytes(self.batch, vocab), dtype=torch.uint8, device=dev)}
         self.gen_graphs = {}
+        self.row_gen_graphs = {}
         self._gen = g
         return g
 
@@ -207,13 +302,16 @@ class GraphedDecoder:
 
     @torch.inference_mode()
     def generate(self, input_ids, max_new_tokens, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
-                 eos_token_id=None, pad_token_id=None, check_every=16):
+                 eos_token_id=None, pad_token_id=None, check_every=16, attention_mask=None):
         """input_ids [batch, prompt] -> [batch, prompt + n] int64 on the device, n <= max_new_tokens; rows that emitted an EOS id
         are padded with pad_token_id (default: the first EOS id) from then on, and the run stops once every row has (HF's
         `generate` semantics).  The prompt is prefilled eagerly and token 1 sampled eagerly from its last position; every later
         token is one replay of the bucket's generation graph.  The host reads the finished flags and the status word once
         every `check_every` tokens -- no host sync per token.  Sampling as ops.sample_tokens: temperature, top_k, top_p,
-        Gumbel-max draw with Philox numbers keyed by (seed, token index, row)."""
+        Gumbel-max draw with Philox numbers keyed by (seed, token index, row).
+        attention_mask [batch, prompt] (0 / 1, see `prefill`): prompts of different lengths; row b's first token is sampled
+        from its logits at its last real position and every row then advances at its own position.  The result is still
+        cat([input_ids, new], 1): for left-padded input, the layout transformers' `generate` returns."""
         input_ids = input_ids.to(self.device)
         if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
             raise ValueError(f"input_ids must be [{self.batch}, prompt], got {tuple(input_ids.shape)}")
@@ -224,7 +322,11 @@ class GraphedDecoder:
         params = ops.sample_params(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, eos_ids=eos,
                                    pad=pad_token_id)
         greedy = not do_sample or float(temperature) <= 0
-        logits = self.prefill(input_ids)
+        ragged = self._ragged(input_ids, attention_mask)
+        logits = self.prefill(input_ids, attention_mask if ragged is not None else None)
+        if ragged is not None:  # the first token of row b comes from its column start_b + L_b - 1
+            last = torch.tensor([s + n - 1 for s, n in zip(*ragged)], dtype=torch.int64, device=self.device)
+            logits = logits[torch.arange(self.batch, device=self.device), last].unsqueeze(1).contiguous()
         g = self._gen_state(logits.shape[-1], max_new_tokens)
         # reset every decoder-owned device word, outside any capture
         g["params"].copy_(params)

@@ -681,15 +681,35 @@ def rmsnorm(x, weight, eps, residual=None, out=None):
     return out
 
 
-def rope_kv_append(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n_kv_heads, head_dim, rotary_dim, pos_dev=None):
+def _check_rows(name, what, rows, shared, B, device):
+    """The per-row position / length words of the *_rows entry points: int32 [B] on the kernel's device, not combined with the
+    shared word."""
+    if shared is not None:
+        raise _lib.AwqHipError(f"{name}: {what}_rows and the shared device word cannot be combined")
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or not rows.is_cuda or rows.device != device:
+        raise _lib.AwqHipError(f"{name}: {what}_rows must be an int32 tensor on {device}")
+    if tuple(rows.shape) != (B,) or not rows.is_contiguous():
+        raise _lib.AwqHipError(f"{name}: {what}_rows must be a contiguous [{B}] tensor, got {tuple(rows.shape)}")
+
+
+def rope_kv_append(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n_kv_heads, head_dim, rotary_dim, pos_dev=None,
+                   pos_rows=None):
     """qkv [B, S, (Hq + 2 Hkv) * D] fp16 -> rotated q [B, S, Hq, D]; rotated k and v are written into
-    the caches [B, Tmax, Hkv, D] at rows start_pos .. start_pos + S - 1 (awq_rope_kv_append)."""
-    _require_gpu(qkv, k_cache, v_cache, cos, sin, pos_dev)
+    the caches [B, Tmax, Hkv, D] at rows start_pos .. start_pos + S - 1 (awq_rope_kv_append).  pos_rows (int32 [B] on the
+    device; start_pos is then ignored): sequence b starts at pos_rows[b] (awq_rope_kv_append_rows)."""
+    _require_gpu(qkv, k_cache, v_cache, cos, sin, pos_dev, pos_rows)
     B, S = qkv.shape[0], qkv.shape[1]
     qkv = qkv.contiguous()
     q = torch.empty((B, S, n_heads, head_dim), dtype=torch.float16, device=qkv.device)
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()) or k_cache.shape[0] < B:
         raise _lib.AwqHipError("rope_kv_append: caches must be contiguous [>=B, Tmax, Hkv, D]")
+    if pos_rows is not None:
+        _check_rows("rope_kv_append", "pos", pos_rows, pos_dev, B, qkv.device)
+        with torch.cuda.device(qkv.device):
+            _lib.check(_lib.lib().awq_rope_kv_append_rows(_ptr(qkv), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(cos), _ptr(sin),
+                                                          _ptr(pos_rows), B, S, n_heads, n_kv_heads, head_dim, rotary_dim,
+                                                          k_cache.shape[1], _stream()), "awq_rope_kv_append_rows")
+        return q
     with torch.cuda.device(qkv.device):
         _lib.check(_lib.lib().awq_rope_kv_append(_ptr(qkv), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(cos), _ptr(sin),
                                                  _ptr(pos_dev), int(start_pos), B, S, n_heads, n_kv_heads, head_dim,
@@ -725,11 +745,13 @@ def prefill_attention(q, k_cache, v_cache, start_pos, scale=None, softcap=0.0, a
 _attn_workspaces = {}
 
 
-def decode_attention(q, k_cache, v_cache, seq_len, scale=None, len_dev=None, max_len=None, softcap=0.0, alibi_slopes=None):
+def decode_attention(q, k_cache, v_cache, seq_len, scale=None, len_dev=None, max_len=None, softcap=0.0, alibi_slopes=None,
+                     len_rows=None):
     """q [B, Hq, 128] fp16, caches [B, Tmax, Hkv, 128] -> [B, Hq, 128]: attention of ONE query token per
     sequence over cache rows [0, seq_len) (awq_decode_attention; with logit soft-capping / ALiBi slopes [Hq] fp32:
-    awq_decode_attention_ex)."""
-    _require_gpu(q, k_cache, v_cache, len_dev, alibi_slopes)
+    awq_decode_attention_ex).  len_rows (int32 [B] on the device; seq_len is then ignored): sequence b attends over rows
+    [0, len_rows[b]), the launch sized for max_len (default: the cache window) -- awq_decode_attention_rows."""
+    _require_gpu(q, k_cache, v_cache, len_dev, alibi_slopes, len_rows)
     B, Hq, D = q.shape
     Hkv, Tmax = k_cache.shape[2], k_cache.shape[1]
     q = q.contiguous()
@@ -745,12 +767,20 @@ def decode_attention(q, k_cache, v_cache, seq_len, scale=None, len_dev=None, max
         _attn_workspaces[key] = ws
     if scale is None:
         scale = D ** -0.5
+    if alibi_slopes is not None:
+        alibi_slopes = alibi_slopes.to(torch.float32).contiguous()
+        if alibi_slopes.numel() != Hq:
+            raise _lib.AwqHipError("decode_attention: alibi_slopes must hold one slope per query head")
+    if len_rows is not None:
+        _check_rows("decode_attention", "len", len_rows, len_dev, B, q.device)
+        with torch.cuda.device(q.device):
+            _lib.check(L.awq_decode_attention_rows(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(len_rows),
+                                                   int(max_len if max_len is not None else Tmax), B, Hq, Hkv, D, Tmax,
+                                                   float(scale), float(softcap), _ptr(alibi_slopes), _ptr(ws), ws.numel(),
+                                                   _stream()), "awq_decode_attention_rows")
+        return out
     with torch.cuda.device(q.device):
         if softcap or alibi_slopes is not None:
-            if alibi_slopes is not None:
-                alibi_slopes = alibi_slopes.to(torch.float32).contiguous()
-                if alibi_slopes.numel() != Hq:
-                    raise _lib.AwqHipError("decode_attention: alibi_slopes must hold one slope per query head")
             _lib.check(L.awq_decode_attention_ex(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(len_dev), int(seq_len),
                                                  int(max_len if max_len is not None else seq_len), B, Hq, Hkv, D, Tmax,
                                                  float(scale), float(softcap), _ptr(alibi_slopes), _ptr(ws), ws.numel(),
@@ -763,11 +793,13 @@ def decode_attention(q, k_cache, v_cache, seq_len, scale=None, len_dev=None, max
 
 
 def decode_attention_rope(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n_kv_heads, pos_dev=None, max_len=None,
-                          scale=None):
+                          scale=None, pos_rows=None):
     """One launch for a decode step: qkv [B, 1, (Hq + 2 Hkv) * 128] (or [B, ...]) -> attention output
     [B, Hq, 128]; rotates q / k, appends k / v at row start_pos and attends over rows [0, start_pos]
-    (awq_decode_attention_rope; bit-identical to rope_kv_append + decode_attention)."""
-    _require_gpu(qkv, k_cache, v_cache, cos, sin, pos_dev)
+    (awq_decode_attention_rope; bit-identical to rope_kv_append + decode_attention).  pos_rows (int32 [B] on the device;
+    start_pos is then ignored): sequence b at position pos_rows[b], the launch sized for max_len (default: the cache window)
+    -- awq_decode_attention_rope_rows."""
+    _require_gpu(qkv, k_cache, v_cache, cos, sin, pos_dev, pos_rows)
     B = qkv.shape[0]
     D = k_cache.shape[3]
     qkv = qkv.contiguous()
@@ -783,6 +815,14 @@ def decode_attention_rope(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n
         _attn_workspaces[key] = ws
     if scale is None:
         scale = D ** -0.5
+    if pos_rows is not None:
+        _check_rows("decode_attention_rope", "pos", pos_rows, pos_dev, B, qkv.device)
+        with torch.cuda.device(qkv.device):
+            _lib.check(L.awq_decode_attention_rope_rows(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(cos), _ptr(sin), _ptr(out),
+                                                        _ptr(pos_rows), int(max_len if max_len is not None else k_cache.shape[1]),
+                                                        B, n_heads, n_kv_heads, D, k_cache.shape[1], float(scale), _ptr(ws),
+                                                        ws.numel(), _stream()), "awq_decode_attention_rope_rows")
+        return out
     with torch.cuda.device(qkv.device):
         _lib.check(L.awq_decode_attention_rope(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(cos), _ptr(sin), _ptr(out),
                                                _ptr(pos_dev), int(start_pos),

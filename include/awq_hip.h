@@ -437,6 +437,32 @@ AWQ_EXPORT int awq_decode_attention_rope(const uint16_t* qkv, uint16_t* k_cache,
                                          int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq,
                                          float scale, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-row positions: batches of sequences of different lengths (modules/fused/decode.py, attention_mask) ------------
+ * The three decode entry points above with ONE position (or length) PER SEQUENCE, read on the device from an int32 array of
+ * B words (pos_rows / len_rows, never NULL).  Everything else is the contract of the shared form:
+ *   awq_rope_kv_append_rows:        sequence b's token s goes to cache row pos_rows[b] + s, rotated by that position; the row is
+ *                                   clamped to [0, max_seq - 1] like a device-side shared position.
+ *   awq_decode_attention_rows:      sequence b attends over cache rows [0, len_rows[b]); softcap / alibi_slopes as in
+ *                                   awq_decode_attention_ex, the ALiBi bias measured from that sequence's own last row
+ *                                   (len_rows[b] - 1).  0 / NULL = plain.
+ *   awq_decode_attention_rope_rows: sequence b is rotated, appended and attended at position pos_rows[b].
+ * max_len (>= every length, <= max_seq) sizes the launch: the split count is chosen from it on the host, and each block deals the
+ * rows of its own sequence to the splits, so a short sequence leaves splits empty (they contribute nothing).  Every sequence's
+ * result is bit-identical to the shared form run on that sequence alone with the same max_len. */
+AWQ_EXPORT int awq_rope_kv_append_rows(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache,
+                                       const float* cos_table, const float* sin_table, const int32_t* pos_rows, int64_t B,
+                                       int64_t S, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim,
+                                       int64_t max_seq, void* stream);
+AWQ_EXPORT int awq_decode_attention_rows(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
+                                         const int32_t* len_rows, int64_t max_len, int64_t B, int64_t n_heads,
+                                         int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, float softcap,
+                                         const float* alibi_slopes, void* workspace, size_t workspace_bytes, void* stream);
+AWQ_EXPORT int awq_decode_attention_rope_rows(const uint16_t* qkv, uint16_t* k_cache, uint16_t* v_cache,
+                                              const float* cos_table, const float* sin_table, uint16_t* out,
+                                              const int32_t* pos_rows, int64_t max_len, int64_t B, int64_t n_heads,
+                                              int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale,
+                                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- one-shot small-message all-reduce for tensor-parallel decode (no reference counterpart: SURVEY.md 2.3 / 8e) ------
  * out[i] = sum over ranks of in_r[i], fp16 with fp32 accumulation in rank order (bitwise identical on every rank), for the
  * [M, hidden] outputs of row-parallel projections (n_halfs % 4 == 0, n_halfs <= max_halfs; <= 64 KiB is what it is built for).

@@ -2,7 +2,8 @@
 """Token generation on the synthetic Llama-2-7B-shape model of tools/bench_decode_model.py: GraphedDecoder.generate (the
 sampler captured into the decode graph, the host looking at the flags every 16 tokens) against the loop users write by hand
 (dec.step + torch.argmax + a per-token .item() EOS check), at several contexts and batch sizes.  Decode tok/s excludes the
-prompt's prefill (timed on its own and subtracted).  --sampler-only times the sampler alone (run it under
+prompt's prefill (timed on its own and subtracted).  --ragged: prompts of different lengths (attention_mask) in one generate
+call, against the same prompts one at a time and a uniform batch padded to the longest prompt.  --sampler-only times the sampler alone (run it under
 `rocprofv3 --kernel-trace --stats` for per-kernel durations)."""
 import argparse, json, os, sys, time
 import torch
@@ -58,6 +59,56 @@ def bench_generate(layers=32, contexts=(64, 2048), batches=(1, 4), new=128):
     return rows
 
 
+def _left_padded(prompts, dev):
+    S = max(p.shape[0] for p in prompts)
+    ids = torch.zeros((len(prompts), S), dtype=torch.int64, device=dev)
+    mask = torch.zeros_like(ids)
+    for b, p in enumerate(prompts):
+        ids[b, S - p.shape[0]:] = p
+        mask[b, S - p.shape[0]:] = 1
+    return ids, mask
+
+
+def bench_ragged(layers=32, batches=(4, 8), new=128, shortest=64, longest=2048):
+    """Prompts spread evenly between `shortest` and `longest` tokens.  'ragged' = one generate call with the attention_mask
+    (per-row positions); 'one at a time' = each prompt through a batch-1 decoder, times summed; 'uniform padded' = the padded
+    batch without a mask (every row at the longest context: what per-row lengths save -- its tokens are NOT correct for the
+    shorter prompts).  Greedy; decode tok/s = batch * (new - 1) / (total - prefill)."""
+    import bench_decode_model
+    from autoawq_amd.modules.fused.decode import GraphedDecoder
+
+    dev = torch.device("cuda")
+    lm, blocks, gen = bench_decode_model.build_model(layers, longest + new + 8, dev, layout="gemv")
+    V = bench_decode_model.V
+    rows = []
+
+    def leg(B, name, lengths, runs):
+        """runs: [(prefill fn, generate fn)], timed one after the other and summed"""
+        t_pre = t_all = 0.0
+        for pre, fn in runs:
+            fn()  # warm-up and captures
+            t_pre += min(_timed(pre)[0] for _ in range(2))
+            t_all += min(_timed(fn)[0] for _ in range(2))
+        r = {"batch": B, "lengths": lengths, "mode": name, "new_tokens": new, "total_s": round(t_all, 5), "prefill_s": round(t_pre, 5),
+             "decode_tok_s": round(B * (new - 1) / max(t_all - t_pre, 1e-9), 1)}
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+
+    for B in batches:
+        lengths = [int(round(shortest + (longest - shortest) * i / (B - 1))) for i in range(B)]
+        prompts = [torch.randint(0, V, (n,), device=dev, generator=gen) for n in lengths]
+        ids, mask = _left_padded(prompts, dev)
+        dec = GraphedDecoder(lm, batch=B)
+        leg(B, "ragged", lengths, [(lambda: dec.prefill(ids, attention_mask=mask), lambda: dec.generate(ids, new, attention_mask=mask))])
+        leg(B, "uniform padded", [longest] * B, [(lambda: dec.prefill(ids), lambda: dec.generate(ids, new))])
+        del dec
+        dec = GraphedDecoder(lm, batch=1)
+        leg(B, "one at a time", lengths, [((lambda p=p: dec.prefill(p.view(1, -1))), (lambda p=p: dec.generate(p.view(1, -1), new)))
+                                          for p in prompts])
+        del dec
+    return rows
+
+
 def bench_sampler(vocabs=(32000, 128256, 152064), batches=(1, 4), calls=200):
     from autoawq_amd import ops
 
@@ -102,10 +153,13 @@ def bench_sampler(vocabs=(32000, 128256, 152064), batches=(1, 4), calls=200):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--sampler-only", action="store_true")
+    ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--new", type=int, default=128)
     a = ap.parse_args()
     if a.sampler_only:
         bench_sampler()
+    elif a.ragged:
+        bench_ragged(layers=a.layers, new=a.new)
     else:
         bench_generate(layers=a.layers, new=a.new)
