@@ -122,6 +122,8 @@ int awq_launch_gemv_batch(const uint16_t* x, const int32_t* qweight, const uint1
 bool awq_gemv_batch_fast_supports(int M, int K, int N, int g);
 int awq_launch_gemv_batch_fast(const uint16_t* x, const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros, uint16_t* y,
                                int M, int K, int N, int g, int group_rows, int depth, hipStream_t st);
+// host only: the plan of a launch (awq_gemv_batch_plan); false where the planner refuses the arguments
+bool awq_gemv_batch_plan_fill(int M, int K, int N, int g, int form, int depth, bool fast, int32_t* out);
 // GEMV layout, prefill-sized batches: the register-decoded MFMA GEMM reading the layout's own buffers (gemm_regb.hip, NK form)
 bool awq_gemm_regb_nk_supports(int M, int K, int N, int g, int ZW);
 int awq_launch_gemm_regb_nk(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,

@@ -421,6 +421,12 @@ int awq_gemv_auto_kernel(int64_t M, int64_t K, int64_t N, int64_t group_size) {
     return awq_gemv_nk_supports(m, k, n, g) ? (int)AWQ_GEMV_KERNEL_TILE16 : -1;
 }
 
+int awq_gemv_batch_plan(int64_t M, int64_t K, int64_t N, int64_t group_size, int32_t form, int32_t depth, int32_t fast, int32_t* out) {
+    if (!out) return AWQ_ERR_NULL;
+    if (M < 1 || M > 128 || K <= 0 || N <= 0 || group_size <= 0 || K > INT32_MAX || N > INT32_MAX || group_size > INT32_MAX) return AWQ_ERR_UNSUPPORTED;
+    return awq_gemv_batch_plan_fill((int)M, (int)K, (int)N, (int)group_size, (int)form, (int)depth, fast != 0, out) ? AWQ_OK : AWQ_ERR_UNSUPPORTED;
+}
+
 int awq_gemv_forward(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
                      uint16_t* y, int64_t M, int64_t K, int64_t N, int64_t group_size, int64_t zeros_width,
                      uint32_t flags, void* stream) {
@@ -446,12 +452,16 @@ int awq_gemv_forward(const uint16_t* x, const int32_t* qweight, const uint16_t* 
         while (cap > 32 && !awq_gemv_batch_supports((int)(M > cap ? cap : M), (int)K, (int)N, (int)group_size)) cap /= 2;
         if (!awq_gemv_batch_supports((int)(M > cap ? cap : M), (int)K, (int)N, (int)group_size)) return AWQ_ERR_UNSUPPORTED;
         g_last_kernel = "gemv_batch";
+        // the tuning bits are the batch kernel's only when the caller picked it: AUTO plans with 0 (flags written for another kernel
+        // must not move the batch kernel's row parts / form / ring depth)
+        const bool tuned = kern == AWQ_GEMV_KERNEL_BATCH;
+        const int form = tuned ? (int)(AWQ_GEMM_FLAG_UNIT(flags) | (AWQ_GEMM_FLAG_WAVES(flags) << 4)) : 0;
+        const int depth = tuned ? (int)AWQ_GEMM_FLAG_SPLITK(flags) : 0;
         const int64_t nchunk = (M + cap - 1) / cap, rows = (M + nchunk - 1) / nchunk;  // balanced chunks of at most `cap` rows
         for (int64_t m0 = 0; m0 < M; m0 += rows) {
             const int mm = (int)(M - m0 < rows ? M - m0 : rows);
             const int rc = awq_launch_gemv_batch(x + m0 * K, qweight, scales, qzeros, y + m0 * N, mm, (int)K, (int)N, (int)group_size,
-                                                 (int)zeros_width, (int)(AWQ_GEMM_FLAG_UNIT(flags) | (AWQ_GEMM_FLAG_WAVES(flags) << 4)),
-                                                 (int)AWQ_GEMM_FLAG_SPLITK(flags), static_cast<hipStream_t>(stream));
+                                                 (int)zeros_width, form, depth, static_cast<hipStream_t>(stream));
             if (rc != AWQ_OK) return rc;
         }
         return AWQ_OK;
@@ -568,12 +578,13 @@ int awq_gemv_fast_forward(const uint16_t* x, const int16_t* qweight, const uint1
     if (kern == AWQ_GEMV_KERNEL_BATCH || (kern == 0 && (M >= 5 || small_ok) && batch_ok)) {
         if (!batch_ok) return AWQ_ERR_UNSUPPORTED;
         g_last_kernel = "gemv_batch_fast";
+        // (tuning bits only when the caller picked the batch kernel: AUTO plans with 0)
+        const int depth = kern == AWQ_GEMV_KERNEL_BATCH ? (int)((AWQ_GEMM_FLAG_SPLITK(flags) & 15u) | (AWQ_GEMM_FLAG_WAVES(flags) << 4)) : 0;
         const int64_t nchunk = (M + fcap - 1) / fcap, rows = (M + nchunk - 1) / nchunk;
         for (int64_t m0 = 0; m0 < M; m0 += rows) {
             const int mm = (int)(M - m0 < rows ? M - m0 : rows);
             const int rc = awq_launch_gemv_batch_fast(x + m0 * K, qweight, scales, qzeros, y + m0 * N, mm, (int)K, (int)N, (int)group_size,
-                                                      (int)group_rows, (int)((AWQ_GEMM_FLAG_SPLITK(flags) & 15u) | (AWQ_GEMM_FLAG_WAVES(flags) << 4)),
-                                                      static_cast<hipStream_t>(stream));
+                                                      (int)group_rows, depth, static_cast<hipStream_t>(stream));
             if (rc != AWQ_OK) return rc;
         }
         return AWQ_OK;

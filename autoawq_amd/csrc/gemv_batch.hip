@@ -332,15 +332,18 @@ __global__ __launch_bounds__(512) void awq_gemv_batch_kernel(BatchParams p) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the chunk has been read: the next one may land on it
                 }
         } else {
+            // (an empty part, M == 0 -- the planner makes none -- reads row 0 instead of the rows at or past the end of x its first row
+            //  names; permute_a zeroes the fragments of rows >= M either way.  A skip of the loads made hipcc copy every fragment register.)
+            const int xrow = M > 0 ? row_base : 0, mlast = max(M - 1, 0);
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
                 for (int u = 0; u < GW; ++u)
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {  // (lanes of batch rows >= M repeat row M - 1's addresses: no more lines per instruction)
-                        const int m = min(16 * mi + n, M - 1);
+                        const int m = min(16 * mi + n, mlast);
                         const int kk = min(128 * (g0 + u) + 32 * kq + 8 * c, p.K - 8);
-                        AWQ_BT_LOAD16(afr[(mi * GW + u) * 4 + c], (AWQ_BT_DBG & 1) ? 0u : (uint32_t)(((row_base + m) * p.K + kk) * 2), p.x);
+                        AWQ_BT_LOAD16(afr[(mi * GW + u) * 4 + c], (AWQ_BT_DBG & 1) ? 0u : (uint32_t)(((xrow + m) * p.K + kk) * 2), p.x);
                     }
             if constexpr (FIRST) {
                 request(0);
@@ -572,10 +575,17 @@ struct BatchPlan {
     size_t ring, pbuf_pitch, ystage;
 };
 
-// form: 0 = auto, 1 = activations through the LDS staging area (XS), 2 = direct fragment loads
+// form: 0 = auto, 1 = activations through the LDS staging area (XS), 2 = direct fragment loads; bits 4 .. 7: the row parts (0 = auto,
+// 1 = as wave groups inside the block, 2 .. 4 = at most that many parts across blocks; 5 .. 15 are refused).  A part holds at most 32
+// rows; no part is ever EMPTY: a forced count the rows cannot fill (M = 5 in four parts of two rows: the fourth would start at row 6)
+// is clamped to the parts the rows fill, ceil(M / rows_part) -- the same rows per part, fewer blocks (M = 1 .. 32: rs = 1 whatever the
+// count, so every forced count runs the same K split and gives the same bits).  AUTO's counts never leave a part empty (17 .. 32 rows
+// in two parts, 33 .. 128 in two to four parts of >= 17 rows); tests/test_gemv_batch_plan_cpu.py checks every plan through
+// awq_gemv_batch_plan.
 bool plan_batch(int M, int K, int N, int g, int form, int rd_req, BatchPlan* out, bool fast = false) {
     if (M < 1 || M > 128 || N < 1 || K < 128 || K % 128 || g != 128) return false;
     const int parts_req = (form >> 4) & 15;         // 0 = auto, 1 = every part inside the block, 2 .. 4 = that many parts across blocks
+    if (parts_req > 4) return false;
     form &= 15;
     if (fast && (N % 16 || form == 2)) return false;  // GEMVFast: whole 4-row bundles, staged form only
     if ((int64_t)N * K / 2 >= ((int64_t)1 << 31) || (int64_t)M * K * 2 >= ((int64_t)1 << 31)) return false;  // 32-bit lane offsets
@@ -591,6 +601,7 @@ bool plan_batch(int M, int K, int N, int g, int form, int rd_req, BatchPlan* out
     b.brs = parts_req >= 2 ? parts_req : (parts_req == 1 ? 1 : auto_brs);
     b.rs = b.brs > 1 ? 1 : nparts;
     b.rows_part = (M + b.rs * b.brs - 1) / (b.rs * b.brs);
+    if (b.brs > 1) b.brs = (M + b.rows_part - 1) / b.rows_part;  // (forced counts only: no empty part, see above; may leave one part)
     if (b.rows_part > 32) return false;
     const int MP = b.rows_part;                     // rows a wave group holds
     b.MI = MP > 16 ? 2 : 1;
@@ -630,7 +641,7 @@ bool plan_batch(int M, int K, int N, int g, int form, int rd_req, BatchPlan* out
     // ring slots, AUTO: two (lazy) wherever they fit, else one -- the per-wave phase times (profiles/r06_gemv_batch_trace.txt) show no
     // wave waiting for a piece in either form: a unit is bound by what the two waves of a SIMD issue (requests, decode, MFMA, exchange);
     // one slot and two measure within 1 - 3 % of each other (profiles/r06_batch_parts.txt)
-    int rd = (rd_req >= 1 && rd_req <= 3) ? rd_req : 2;
+    int rd = (rd_req >= 1 && rd_req <= (fast ? 2 : 3)) ? rd_req : 2;  // (GEMVFast: slots 1 | 2 only -- a larger request takes 2)
     while (rd > 1 && fixed + (size_t)8 * rd * PIECE_B > budget) --rd;
     if (fixed + (size_t)8 * rd * PIECE_B > budget) return false;
     b.RD = rd;
@@ -710,12 +721,22 @@ bool awq_gemv_batch_fast_supports(int M, int K, int N, int g) {
     return plan_batch(M, K, N, g, 0, 0, &b, true);
 }
 
+// host only (awq_gemv_batch_plan): the plan a launch with these arguments runs -- brs, rs, rows_part, MI, wk, passes, blocks,
+// tiles_base, tiles_rem, lds_bytes, wt, RD, XS, tiles_max, xs_rows (AWQ_GEMV_BATCH_PLAN_FIELDS int32)
+bool awq_gemv_batch_plan_fill(int M, int K, int N, int g, int form, int depth, bool fast, int32_t* out) {
+    BatchPlan b;
+    if (!plan_batch(M, K, N, g, form, depth, &b, fast)) return false;
+    const int32_t f[15] = {b.brs, b.rs, b.rows_part, b.MI, b.wk, b.passes, b.blocks, b.tiles_base, b.tiles_rem,
+                           (int32_t)(b.ring + 8 * b.pbuf_pitch + b.ystage), b.wt, b.RD, b.XS, b.tiles_max, b.xs_rows};
+    for (int i = 0; i < 15; ++i) out[i] = f[i];
+    return true;
+}
+
 // the same kernel on the GEMVFast layout's buffers (qweight int16 [N/4, K], scales / qzeros fp16 [group_rows, N]); depth 1 | 2
 int awq_launch_gemv_batch_fast(const uint16_t* x, const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros, uint16_t* y,
                                int M, int K, int N, int g, int group_rows, int depth, hipStream_t st) {
     if (group_rows < K / 128) return AWQ_ERR_BAD_SHAPE;
     const int parts = (depth >> 4) & 15;  // (row parts across blocks: see plan_batch)
     depth &= 15;
-    if (depth > 2) depth = 2;
     return launch_batch(x, qweight, scales, qzeros, y, M, K, N, g, 0, group_rows, parts << 4, depth, true, st);
 }

@@ -218,7 +218,9 @@ AWQ_EXPORT int awq_moe_sort_pairs(const int32_t* topk_ids, int32_t* order, int32
                                      _UNIT: how the activations reach the registers (1 = coalesced LDS-DMA into a wave-private staging
                                      area, 2 = direct 16-byte fragment loads; 0 = auto: staged when it fits), _SPLITK: ring slots per wave
                                      (1 .. 3), _WAVES: the row parts (0 = auto, 1 = as wave groups inside one block -- round 6's first
-                                     form --, 2 .. 4 = that many parts across blocks; refused where a part would exceed 32 rows) */
+                                     form --, 2 .. 4 = that many parts across blocks, fewer where the rows would leave a part empty;
+                                     refused where a part would exceed 32 rows, and 5 .. 15).  These bits are read only when
+                                     AWQ_GEMM_FLAG_KERNEL names this kernel: AUTO plans with 0 (they belong to the other kernels there) */
 #define AWQ_GEMV_KERNEL_PREFILL 4u /* any M in ONE call: the register-decoded MFMA GEMM on this layout's own buffers (gemm_regb.hip, NK
                                      form; K % 64 == 0, group_size % 64 == 0, N % 4 == 0); _NLOG = 2: 256-row tiles.  EXPLICIT only:
                                      measured 0.29 of the MFMA peak at M = 16384 (dequantise + dense GEMM: 0.42) and latency-bound
@@ -226,6 +228,15 @@ AWQ_EXPORT int awq_moe_sort_pairs(const int32_t* topk_ids, int32_t* order, int32
 /* Which AWQ_GEMV_KERNEL_* the AUTO dispatch of awq_gemv_forward takes for this shape (host only; -1: none takes it).  A pure
  * function of its arguments -- what awq_hip_last_kernel (a per-thread diagnostic) reports after the call. */
 AWQ_EXPORT int awq_gemv_auto_kernel(int64_t M, int64_t K, int64_t N, int64_t group_size);
+/* The plan one launch of the batched kernel (csrc/gemv_batch.hip, <= 128 rows) runs for these arguments (host only, no GPU):
+ * form = _UNIT | (_WAVES << 4) and depth = _SPLITK of an AWQ_GEMV_KERNEL_BATCH call; fast != 0: the GEMVFast form (the form's low
+ * four bits are 0 there).  AWQ_OK fills out[AWQ_GEMV_BATCH_PLAN_FIELDS] = brs (row parts across blocks), rs (row parts inside a
+ * block), rows_part, MI (16-row tiles per part), wk (waves side by side on a tile), passes over K, blocks, tiles_base, tiles_rem
+ * (column tiles per owner), lds_bytes, wt (tile owners' wave groups per block), RD (ring slots), XS (1: staged activations),
+ * tiles_max, xs_rows; AWQ_ERR_UNSUPPORTED where the planner refuses them (the launch would return the same). */
+#define AWQ_GEMV_BATCH_PLAN_FIELDS 15
+AWQ_EXPORT int awq_gemv_batch_plan(int64_t M, int64_t K, int64_t N, int64_t group_size, int32_t form, int32_t depth, int32_t fast,
+                                   int32_t* out);
 AWQ_EXPORT int awq_gemv_forward(const uint16_t* x, const int32_t* qweight, const uint16_t* scales,
                                 const int32_t* qzeros, uint16_t* y, int64_t M, int64_t K, int64_t N,
                                 int64_t group_size, int64_t zeros_width, uint32_t flags, void* stream);
@@ -251,7 +262,7 @@ AWQ_EXPORT int awq_repack_gemv_to_gemm(const int32_t* qweight, const uint16_t* s
  * small M, awq_v2_ext.gemm_forward_cuda_prefill (gemv_fast.py:185-208).  y [M, N] = x [M, K] @ W^T with
  * W = w*s + qzeros; N % 16 == 0, K % 128 == 0.  group_rows = rows of scales / qzeros (8*ZW).  AUTO (AWQ_GEMM_FLAG_KERNEL 0): from
  * M = 5 the batched kernel (gemv_batch.hip in its GEMVFast form, group_size 128: ANY M in one call, launches of <= 128 rows;
- * also AWQ_GEMV_KERNEL_BATCH explicitly, _SPLITK = ring slots 1 | 2, _WAVES = the row parts as above); below that, or with AWQ_GEMM_FLAG_KERNEL = 1, the 16-row kernel
+ * also AWQ_GEMV_KERNEL_BATCH explicitly, _SPLITK = ring slots 1 | 2, _WAVES = the row parts as above; AUTO reads neither); below that, or with AWQ_GEMM_FLAG_KERNEL = 1, the 16-row kernel
  * (gemv_fast.hip: 1 <= M <= 16 per call, the host wrapper chunks). */
 AWQ_EXPORT int awq_gemv_fast_forward(const uint16_t* x, const int16_t* qweight, const uint16_t* scales,
                                      const uint16_t* qzeros, uint16_t* y, int64_t M, int64_t K, int64_t N,

@@ -27,7 +27,8 @@ COMPACT = ("(test_gemv_rows_kernel_vs_oracle and (4096-4096-128 or 11008-4096-12
            "(test_gemvfast_layout_prefill_route_vs_oracle and (1-1024-200 or 1-512-64 or 1-4096-4096)) or "  # round 6: the FZ form + its repack, ragged N
            "(test_grouped_rows_kernel_vs_oracle and (5-3-512-250 or 4-2-14336-256 or 1-2-1024-96)) or test_grouped_prefill_gather_scatter or "  # round 6: MoE decode twins,
            "test_moe_sort_pairs or test_moe_route_routing_only or "                                                                                # the index-list prefill
-           "test_gemv_batch_refuses or repack or prefill_attention or test_decode_attention_vs_oracle or unpack or "
+           "test_gemv_batch_refuses or test_gemv_batch_forced_parts_small_m or test_gemv_batch_rows_beyond_m or "  # the row parts at small M,
+           "test_gemv_batch_auto_ignores_foreign_tuning_bits or repack or prefill_attention or test_decode_attention_vs_oracle or unpack or "
            "test_dequant_golden or test_gemm_golden or test_moe_block_vs_oracle or rmsnorm or rope_kv or test_gemvfast_layout_golden")
 
 

@@ -812,6 +812,106 @@ def test_gemv_batch_refuses_what_it_cannot_take(ops):
         assert ops.last_kernel() == "gemv_nk"
 
 
+# ---- the row parts at the small-M end, rows beyond M, AUTO and foreign tuning bits (both layouts; tests/test_gemv_batch_plan_cpu.py
+#      checks every plan on the host -- an empty part reads no value into the output, so only the plan shows it)
+# a ragged N (GEMVFast: 13 tiles, 33 groups), several passes over K, the benched shape
+PARTS_SHAPES = {"gemv": [(2048, 4099), (11008, 4096), (4096, 11008)], "gemvfast": [(4224, 208), (11008, 4096), (4096, 11008)]}
+
+
+def _batch_case(oracle, layout, K, N, M, seed):
+    """device buffers, a forward(x, flags) on them and the exact product of `x`'s rows"""
+    g = 128
+    if layout == "gemv":
+        qw, qz, sc, x = gemv_case(K, N, g, M, seed)
+        yex = oracle.matmul_exact_gemv(x.numpy(), qw.numpy(), qz.numpy(), sc.numpy(), g) if oracle is not None else None
+        qwc, qzc, scc = qw.cuda(), qz.cuda(), sc.cuda()
+        from autoawq_amd import ops
+
+        fwd = lambda xx, f: ops.gemv_forward(xx, qwc, scc, qzc, g, flags=f)
+        return x, yex, fwd, "gemv_batch"
+    qw, sc, qz, x = gemvfast_case(K, N, g, M, seed)
+    yex = oracle.matmul_exact_gemvfast(x.numpy(), qw.numpy(), sc.numpy(), qz.numpy(), g) if oracle is not None else None
+    qwc, scc, qzc = qw.cuda(), sc.cuda(), qz.cuda()
+    from autoawq_amd import ops
+
+    fwd = lambda xx, f: ops.gemv_fast_forward(xx, qwc, scc, qzc, g, flags=f)
+    return x, yex, fwd, "gemv_batch_fast"
+
+
+@pytest.mark.parametrize("layout", ["gemv", "gemvfast"])
+@pytest.mark.parametrize("shape", [0, 1, 2])
+def test_gemv_batch_forced_parts_small_m(ops, oracle, layout, shape):
+    """Forced row-part counts at M = 1 .. 16 (_WAVES = 1: inside the block, 2 .. 4: across blocks; a count the rows cannot fill is
+    clamped so that no part is empty, 5 .. 15 are refused): within 1 ulp + 1e-4 rms of the exact product, and -- every part of <= 32
+    rows runs rs = 1 and the same K split -- bitwise equal whatever the count, AUTO included.  x is an allocation of exactly M rows
+    (the guard-band leg puts unmapped memory right behind it)."""
+    K, N = PARTS_SHAPES[layout][shape]
+    xall, yex_all, fwd, name = _batch_case(oracle, layout, K, N, 16, seed=K + 5 * N)
+    bt = ops.gemm_flags(kernel=GEMV_KERNEL_BATCH)
+    for M in (1, 2, 3, 5, 7, 9, 13, 16):
+        x = xall[:M].clone().cuda()
+        ys = {}
+        for w in (0, 1, 2, 3, 4):
+            ys[w] = fwd(x, bt | ops.gemm_flags(waves=w))
+            assert ops.last_kernel() == name
+            assert_close_to_exact(ys[w].cpu().numpy(), yex_all[:M], f"{layout} K{K} N{N} M{M} parts {w} vs exact")
+        for w in (1, 2, 3, 4):
+            assert torch.equal(ys[w], ys[0]), f"{layout} K{K} N{N} M{M}: {w} row parts differ from AUTO"
+        for w in range(5, 16):
+            with pytest.raises(Exception, match="code -3"):
+                fwd(x, bt | ops.gemm_flags(waves=w))
+
+
+@pytest.mark.parametrize("layout", ["gemv", "gemvfast"])
+def test_gemv_batch_rows_beyond_m(ops, oracle, layout):
+    """x = buf[:M] where buf goes on with rows of NaN and 65504: no such row may reach an output -- every output is finite and equal
+    to the product of a clean copy of x (AUTO and forced row parts, M across the 16-row tiles and the part boundaries)."""
+    K, N = PARTS_SHAPES[layout][0]
+    MX = 128
+    xall, yex_all, fwd, name = _batch_case(oracle, layout, K, N, MX, seed=K + 11 * N)
+    bt = ops.gemm_flags(kernel=GEMV_KERNEL_BATCH)
+    for M in (1, 5, 16, 17, 33, 64, 100, 127):
+        buf = torch.empty((M + 24, K), dtype=torch.float16)
+        buf[:M] = xall[:M]
+        buf[M::2] = float("nan")
+        buf[M + 1::2] = 65504.0
+        buf = buf.cuda()
+        x = buf[:M]
+        clean = xall[:M].clone().cuda()
+        for w in (0, 1, 2, 3, 4):
+            f = bt | ops.gemm_flags(waves=w)
+            try:
+                want = fwd(clean, f)
+            except Exception as e:  # (a part of more than 32 rows, or in-block parts whose tile lists overflow LDS)
+                assert "code -3" in str(e) and ((w >= 2 and (M + w - 1) // w > 32) or (w == 1 and M > 32)), (e, M, w)
+                continue
+            y = fwd(x, f)
+            assert ops.last_kernel() == name
+            assert bool(torch.isfinite(y).all()), f"{layout} M{M} parts {w}: a row beyond M reached the output"
+            assert torch.equal(y, want), f"{layout} M{M} parts {w}: rows beyond M changed the output"
+            if w == 0:
+                assert_close_to_exact(y.cpu().numpy(), yex_all[:M], f"{layout} K{K} N{N} M{M} beyond-M vs exact")
+
+
+@pytest.mark.parametrize("layout", ["gemv", "gemvfast"])
+@pytest.mark.parametrize("shape", [0, 1, 2])
+def test_gemv_batch_auto_ignores_foreign_tuning_bits(ops, layout, shape):
+    """On AUTO (_KERNEL 0) the _WAVES / _UNIT / _SPLITK bits belong to other kernels (gemv_rows, gemv_nk, gemv_fast ...): where AUTO
+    picks the batched kernel they change neither the kernel nor a bit of the result."""
+    K, N = PARTS_SHAPES[layout][shape]
+    xall, _, fwd, name = _batch_case(None, layout, K, N, 128, seed=K + 13 * N)
+    grid = [(1, 1, 1), (2, 2, 3), (4, 0, 2), (8, 4, 0), (15, 15, 255), (5, 1, 8), (0, 2, 1), (3, 8, 0)]
+    for M in (5, 9, 16, 24, 33, 64, 100, 128):
+        x = xall[:M].clone().cuda()
+        y0 = fwd(x, 0)
+        k0 = ops.last_kernel()
+        assert k0 == name, (layout, K, N, M, k0)
+        for w, u, s in grid:
+            y = fwd(x, ops.gemm_flags(waves=w, unit=u, splitk=s))
+            assert ops.last_kernel() == k0, (layout, M, w, u, s)
+            assert torch.equal(y, y0), f"{layout} K{K} N{N} M{M}: AUTO followed waves={w} unit={u} splitk={s}"
+
+
 @pytest.mark.parametrize("K,N,g", [(4096, 11008, 128), (11008, 4096, 128), (1024, 200, 128), (512, 264, 64), (256, 8, 32), (2048, 4104, 2048), (8192, 1280, 128)])
 def test_repack_gemv_to_gemm_bit_exact(ops, oracle, K, N, g):
     """csrc/repack.hip (the prefill route of WQLinear_GEMV: GEMV-layout buffers -> a GEMM-layout temporary of the call): the packed
