@@ -47,6 +47,17 @@ class AwqSampleArgs(ctypes.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("stream", c_void_p)]
 
 
+class AwqSampleProc(ctypes.Structure):
+    """struct AwqSampleProc of include/awq_hip.h (same field order; lives in device memory)."""
+    _fields_ = [("repetition_penalty", c_float), ("min_new_tokens", ctypes.c_int32), ("pad", ctypes.c_int32 * 2)]
+
+
+class AwqSampleProcArgs(ctypes.Structure):
+    """struct AwqSampleProcArgs of include/awq_hip.h (same field order)."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("proc", c_void_p), ("history", c_void_p),
+                ("history_stride", c_int64)]
+
+
 # name -> (restype, argtypes); must list every symbol include/awq_hip.h declares
 # (tests/test_boundary.py cross-checks this table against the header and the .so).
 SIGNATURES = {
@@ -113,6 +124,8 @@ SIGNATURES = {
     "awq_gemm_auto_kernel": (c_int, [c_int64, c_int64, c_int64, c_int64]),
     "awq_sample_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "awq_sample_tokens": (c_int, [ctypes.POINTER(AwqSampleArgs)]),
+    "awq_sample_tokens_ex": (c_int, [ctypes.POINTER(AwqSampleArgs), ctypes.POINTER(AwqSampleProcArgs)]),
+    "awq_sample_history_seed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),
 }
 
 

@@ -32,8 +32,27 @@
 //   pass 3: Gumbel scores of the kept tokens: the best above the top-p bin, and per low byte of the top-p bin its best score
 //           and mass.  The combine fixes the top-p threshold inside the bin, takes the winner and does the bookkeeping.
 // Passes 2 and 3 return at once when the parameters say greedy, so one captured graph serves either configuration.
+//
+// Logit processors (awq_sample_tokens_ex; pinned by tests/test_sampling_penalty_cpu.py and tests/test_gpu_sampling_penalty.py):
+// transformers' RepetitionPenaltyLogitsProcessor then MinNewTokensLengthLogitsProcessor, which `generate` applies to the fp32 cast
+// of the logits before the warpers (greedy too).  For row r at token index t (read at block start: the launch's last row
+// advances t only after every block of every row has arrived) the logit i with fp16 bits h is processed as
+//   1. t <= min_new_tokens and i one of the n_eos EOS ids: h = -inf (new-token count t - 1 < min_new_tokens);
+//   2. otherwise, bit i of history row r set and h finite: v = float(h), v = v < 0 ? v * p : v / p in fp32 (the correctly
+//      rounded division: no __fdividef / rcp), then fp16 round-to-nearest-even saturating to +-65504 -- a finite logit stays
+//      finite (a penalty below 1 cannot make a +inf that would set the status bit), +-0 keep their sign (the key folds them);
+//      -inf, +inf and NaN pass unchanged, so the status rules above are unchanged.
+//   Every pass, and the greedy argmax, reads the processed value (process8 after each load8): the contract above applied to
+//   process(logits).  Tie rule: the processed value is exactly fp16(transformers' fp32 value) wherever that is in range, so the
+//   token equals transformers' on rows where no two candidates collide after that rounding (as for the top-p boundary rule).
+//   Bookkeeping: finish_row ORs the bit of the token written to out[row] into history row r (every row, the pad of a finished or
+//   failed row included, as transformers' input_ids carry it; a pad outside [0, V) sets nothing), after every block of the row
+//   has read the history.  awq_sample_history_seed ORs an id matrix into a history (a prompt).
+// The PROC = false instantiations are the kernels of awq_sample_tokens, instruction for instruction.
 #include "awq_device.h"
 #include "awq_internal.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -91,6 +110,14 @@ struct Ctx {
     uint32_t* status;
     char* ws;
 };
+
+// The processors' arguments (PROC = true).  A separate type, so that the PROC = false kernels keep Ctx and their argument layout.
+struct ProcCtx : Ctx {
+    const AwqSampleProc* proc;
+    uint32_t* history;
+    int64_t history_stride;
+};
+template <bool PROC> using CtxT = typename std::conditional<PROC, ProcCtx, Ctx>::type;
 
 AWQ_DEV WsHead* head_of(const Ctx& c) { return reinterpret_cast<WsHead*>(c.ws); }
 AWQ_DEV RowWs* row_of(const Ctx& c, int r) { return reinterpret_cast<RowWs*>(c.ws + kHeadBytes + (size_t)r * kRowBytes); }
@@ -180,6 +207,35 @@ AWQ_DEV void load8(const Ctx& c, int row, int i0, uint32_t h[8]) {
     }
 }
 
+// The processors (PROC) on the 8 logits of this thread.  eos_on: t <= min_new_tokens (block-uniform).  The history bits of
+// i0 .. i0 + 7 are one byte (i0 % 8 == 0): bit v % 8 of byte v / 8 is bit v % 32 of word v / 32 (little endian).
+AWQ_DEV void process8(const ProcCtx& c, const AwqSampleParams& P, int row, int i0, bool eos_on, uint32_t h[8]) {
+    if (eos_on) {
+        const int n = P.n_eos < 8 ? P.n_eos : 8;
+        for (int e = 0; e < n; ++e) {
+            const int d = P.eos[e] - i0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (d == j) h[j] = 0xFC00u;
+        }
+    }
+    const float p = c.proc->repetition_penalty;
+    if (p == 1.f || i0 >= c.V) return;  // (p = 1: v * 1 and v / 1 are v, and fp16(float(h)) is h)
+    const uint32_t bits = reinterpret_cast<const uint8_t*>(c.history + (int64_t)row * c.history_stride)[i0 >> 3];
+    if (!bits) return;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (!((bits >> j) & 1u) || (h[j] & 0x7FFFu) >= 0x7C00u) continue;
+        float v = (float)__builtin_bit_cast(half_t, (uint16_t)h[j]);
+        v = v < 0.f ? v * p : v / p;
+        v = fminf(fmaxf(v, -65504.f), 65504.f);
+        h[j] = __builtin_bit_cast(uint16_t, (half_t)v);
+    }
+}
+
+// t <= min_new_tokens, read at block start
+AWQ_DEV bool eos_suppressed(const ProcCtx& c) { return ld(c.t) <= c.proc->min_new_tokens; }
+
 AWQ_DEV bool is_greedy(const AwqSampleParams& P, int forced) { return forced || P.do_sample == 0 || !(P.temperature > 0.f); }
 
 // The block's arrival on the row counter: true in the last block of the row, after an acquire (the other blocks' atomics are
@@ -213,7 +269,8 @@ AWQ_DEV void set_status(const Ctx& c, int row) {
 // from the logits (not the pad of a finished or failed row) -- only then can it latch `finished`.  Nothing written here is
 // read by another block of this launch (the next launch reads it), so the launch counter needs no fence; t is read, and
 // its load drained, before this row's add, and only the last add's row writes t.
-AWQ_DEV void finish_row(const Ctx& c, int row, const AwqSampleParams& P, int64_t tok, bool sampled) {
+template <bool PROC>
+AWQ_DEV void finish_row(const CtxT<PROC>& c, int row, const AwqSampleParams& P, int64_t tok, bool sampled) {
     RowWs* w = row_of(c, row);
     const RowState zero{};
     w->st = zero;
@@ -225,6 +282,11 @@ AWQ_DEV void finish_row(const Ctx& c, int row, const AwqSampleParams& P, int64_t
         const int n = P.n_eos < 8 ? P.n_eos : 8;
         for (int e = 0; e < n; ++e)
             if (tok == P.eos[e]) c.finished[row] = 1;
+    }
+    if constexpr (PROC) {  // every block of the row has read its history (they all arrived before this combine)
+        if (tok >= 0 && tok < c.V)
+            __hip_atomic_fetch_or(c.history + row * c.history_stride + (tok >> 5), 1u << (tok & 31), __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_AGENT);
     }
     WsHead* h = head_of(c);
     if (__hip_atomic_fetch_add(&h->arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)c.B - 1) {
@@ -271,10 +333,13 @@ AWQ_DEV uint32_t find_from_top(Get get, unsigned long long base, Ok ok, unsigned
 }
 
 // ---- pass 1 ----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void sample_pass1(Ctx c, int greedy_forced) {
+template <bool PROC>
+__global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC> c, int greedy_forced) {
     const int row = blockIdx.y, tid = threadIdx.x;
     const AwqSampleParams& P = *c.params;  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
     const bool greedy = is_greedy(P, greedy_forced);
+    bool eos_on = false;
+    if constexpr (PROC) eos_on = eos_suppressed(c);
     RowWs* w = row_of(c, row);
     const bool fin = c.finished && c.finished[row] != 0;
     __shared__ uint32_t s_cnt[256];
@@ -287,6 +352,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass1(Ctx c, int greedy_force
         const int i0 = blockIdx.x * kChunk + tid * kPerThread;
         uint32_t h[8];
         load8(c, row, i0, h);
+        if constexpr (PROC) process8(c, P, row, i0, eos_on, h);
         unsigned long long best = 0;
         uint32_t bad = 0;
 #pragma unroll
@@ -333,7 +399,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass1(Ctx c, int greedy_force
     const bool live = !fin && !bad && best != 0;
     if (!fin && !live && tid == 0) set_status(c, row);
     if (greedy) {
-        if (tid == 0) finish_row(c, row, P, live ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, live);
+        if (tid == 0) finish_row<PROC>(c, row, P, live ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, live);
         return;
     }
     __shared__ uint32_t s_hist[256];
@@ -361,10 +427,13 @@ __global__ __launch_bounds__(kThreads) void sample_pass1(Ctx c, int greedy_force
 }
 
 // ---- pass 2 ----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void sample_pass2(Ctx c, int greedy_forced) {
+template <bool PROC>
+__global__ __launch_bounds__(kThreads) void sample_pass2(CtxT<PROC> c, int greedy_forced) {
     const int row = blockIdx.y, tid = threadIdx.x;
     const AwqSampleParams& P = *c.params;  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
     if (is_greedy(P, greedy_forced)) return;
+    bool eos_on = false;
+    if constexpr (PROC) eos_on = eos_suppressed(c);
     RowWs* w = row_of(c, row);
     const RowState S = w->st;
     const bool topp = P.top_p < 1.f;
@@ -380,6 +449,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass2(Ctx c, int greedy_force
         const int i0 = blockIdx.x * kChunk + tid * kPerThread;
         uint32_t h[8];
         load8(c, row, i0, h);
+        if constexpr (PROC) process8(c, P, row, i0, eos_on, h);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             if ((h[j] & 0x7FFFu) >= 0x7C00u) continue;
@@ -447,10 +517,13 @@ __global__ __launch_bounds__(kThreads) void sample_pass2(Ctx c, int greedy_force
 }
 
 // ---- pass 3 ----------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void sample_pass3(Ctx c, int greedy_forced) {
+template <bool PROC>
+__global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC> c, int greedy_forced) {
     const int row = blockIdx.y, tid = threadIdx.x;
     const AwqSampleParams& P = *c.params;  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
     if (is_greedy(P, greedy_forced)) return;
+    bool eos_on = false;
+    if constexpr (PROC) eos_on = eos_suppressed(c);
     RowWs* w = row_of(c, row);
     const RowState S = w->st;
     const bool topp = S.bin_p != kNone && P.top_p < 1.f;
@@ -464,6 +537,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass3(Ctx c, int greedy_force
         const int i0 = blockIdx.x * kChunk + tid * kPerThread;
         uint32_t h[8];
         load8(c, row, i0, h);
+        if constexpr (PROC) process8(c, P, row, i0, eos_on, h);
         const uint32_t lo_key = topp ? (S.bin_p << 8) : S.tau_k;
         const uint32_t tau = lo_key > S.tau_k ? lo_key : S.tau_k;
         unsigned long long best = 0;
@@ -519,7 +593,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass3(Ctx c, int greedy_force
     if (tid == 0) st(&w->best_above, 0ull);
     if (tid >= 64) return;
     if (S.mode != MODE_LIVE) {
-        if (tid == 0) finish_row(c, row, P, (int64_t)P.pad, false);
+        if (tid == 0) finish_row<PROC>(c, row, P, (int64_t)P.pad, false);
         return;
     }
     uint32_t lo_p = 0;
@@ -537,7 +611,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass3(Ctx c, int greedy_force
     best = above_best > best ? above_best : best;
     if (tid == 0) {
         if (!best) set_status(c, row);
-        finish_row(c, row, P, best ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, best != 0);
+        finish_row<PROC>(c, row, P, best ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, best != 0);
     }
 }
 
@@ -548,7 +622,10 @@ size_t awq_sample_workspace_bytes(int64_t B, int64_t V) {
     return kHeadBytes + (size_t)B * kRowBytes;
 }
 
-int awq_sample_tokens(const AwqSampleArgs* a) {
+namespace {
+
+// validation of the launch arguments shared by awq_sample_tokens and awq_sample_tokens_ex; AWQ_OK and *c filled, or the error
+int sample_ctx(const AwqSampleArgs* a, Ctx* c) {
     if (!a) return AWQ_ERR_NULL;
     if (a->struct_bytes != sizeof(AwqSampleArgs)) return AWQ_ERR_BAD_SHAPE;
     if (a->B < 1 || a->B > kMaxRows || a->V < 1 || a->V > kMaxVocab) return AWQ_ERR_UNSUPPORTED;
@@ -558,27 +635,80 @@ int awq_sample_tokens(const AwqSampleArgs* a) {
     if (a->workspace_bytes < awq_sample_workspace_bytes(a->B, a->V)) return AWQ_ERR_WORKSPACE;
     if (((uintptr_t)a->workspace & 255u) != 0) return AWQ_ERR_BAD_ALIGNMENT;
     if (((uintptr_t)a->logits & 1u) != 0) return AWQ_ERR_BAD_ALIGNMENT;
-    Ctx c{};
-    c.logits = a->logits;
-    c.row_stride = a->row_stride;
-    c.V = (int)a->V;
-    c.B = (int)a->B;
-    c.params = a->params;
-    c.t = a->t;
-    c.out = a->out;
-    c.out_stride = a->out_stride;
-    c.ring = a->ring;
-    c.ring_cap = a->ring_cap;
-    c.finished = a->finished;
-    c.status = a->status;
-    c.ws = static_cast<char*>(a->workspace);
+    *c = Ctx{};
+    c->logits = a->logits;
+    c->row_stride = a->row_stride;
+    c->V = (int)a->V;
+    c->B = (int)a->B;
+    c->params = a->params;
+    c->t = a->t;
+    c->out = a->out;
+    c->out_stride = a->out_stride;
+    c->ring = a->ring;
+    c->ring_cap = a->ring_cap;
+    c->finished = a->finished;
+    c->status = a->status;
+    c->ws = static_cast<char*>(a->workspace);
+    return AWQ_OK;
+}
+
+template <bool PROC>
+int sample_run(const AwqSampleArgs* a, const CtxT<PROC>& c) {
     const hipStream_t s = static_cast<hipStream_t>(a->stream);
     const int greedy = (a->flags & AWQ_SAMPLE_FLAG_GREEDY) != 0;
     const dim3 grid((unsigned)((a->V + kChunk - 1) / kChunk), (unsigned)a->B);
-    hipLaunchKernelGGL(sample_pass1, grid, dim3(kThreads), 0, s, c, greedy);
+    hipLaunchKernelGGL(sample_pass1<PROC>, grid, dim3(kThreads), 0, s, c, greedy);
     if (!greedy) {
-        hipLaunchKernelGGL(sample_pass2, grid, dim3(kThreads), 0, s, c, 0);
-        hipLaunchKernelGGL(sample_pass3, grid, dim3(kThreads), 0, s, c, 0);
+        hipLaunchKernelGGL(sample_pass2<PROC>, grid, dim3(kThreads), 0, s, c, 0);
+        hipLaunchKernelGGL(sample_pass3<PROC>, grid, dim3(kThreads), 0, s, c, 0);
     }
+    return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
+}
+
+// one thread per id: ORs bit ids[b, s] of history row b (ids outside [0, V) ignored)
+__global__ __launch_bounds__(kThreads) void sample_history_seed_kernel(uint32_t* history, int64_t history_stride,
+                                                                       const int64_t* ids, int64_t ids_stride, int64_t S,
+                                                                       int64_t V) {
+    const int64_t s = (int64_t)blockIdx.x * kThreads + threadIdx.x, b = blockIdx.y;
+    if (s >= S) return;
+    const int64_t v = ids[b * ids_stride + s];
+    if (v < 0 || v >= V) return;
+    __hip_atomic_fetch_or(history + b * history_stride + (v >> 5), 1u << (v & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+}  // namespace
+
+int awq_sample_tokens(const AwqSampleArgs* a) {
+    Ctx c;
+    const int rc = sample_ctx(a, &c);
+    return rc != AWQ_OK ? rc : sample_run<false>(a, c);
+}
+
+int awq_sample_tokens_ex(const AwqSampleArgs* a, const AwqSampleProcArgs* q) {
+    if (!q) return awq_sample_tokens(a);
+    ProcCtx c;
+    const int rc = sample_ctx(a, &c);
+    if (rc != AWQ_OK) return rc;
+    if (q->struct_bytes != sizeof(AwqSampleProcArgs)) return AWQ_ERR_BAD_SHAPE;
+    if (q->flags != 0) return AWQ_ERR_UNSUPPORTED;
+    if (!q->proc || !q->history) return AWQ_ERR_NULL;
+    if (q->history_stride < (a->V + 31) / 32) return AWQ_ERR_BAD_SHAPE;
+    if (((uintptr_t)q->history & 3u) != 0 || ((uintptr_t)q->proc & 15u) != 0) return AWQ_ERR_BAD_ALIGNMENT;
+    c.proc = q->proc;
+    c.history = q->history;
+    c.history_stride = q->history_stride;
+    return sample_run<true>(a, c);
+}
+
+int awq_sample_history_seed(uint32_t* history, int64_t history_stride, const int64_t* ids, int64_t ids_stride, int64_t B,
+                            int64_t S, int64_t V, void* stream) {
+    if (B < 0 || B > kMaxRows || S < 0 || S > 0x7FFFFFFF || V < 1 || V > kMaxVocab) return AWQ_ERR_UNSUPPORTED;
+    if (B == 0 || S == 0) return AWQ_OK;
+    if (!history || !ids) return AWQ_ERR_NULL;
+    if (history_stride < (V + 31) / 32 || (B > 1 && ids_stride < S)) return AWQ_ERR_BAD_SHAPE;
+    if (((uintptr_t)history & 3u) != 0 || ((uintptr_t)ids & 7u) != 0) return AWQ_ERR_BAD_ALIGNMENT;
+    const dim3 grid((unsigned)((S + kThreads - 1) / kThreads), (unsigned)B);
+    hipLaunchKernelGGL(sample_history_seed_kernel, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), history,
+                       history_stride, ids, ids_stride, S, V);
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }

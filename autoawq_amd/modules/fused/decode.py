@@ -34,6 +34,10 @@ picks the bucket from the largest and rolls a row's window on its own when that 
 an all-ones mask, takes the shared words and the graphs above unchanged.
 
     out = dec.generate(ids, attention_mask=mask, max_new_tokens=64)   # left-padded ids: transformers' layout
+
+repetition_penalty / min_new_tokens (transformers' logit processors) run inside the sampler's passes, reading a per-row bitmap of
+the ids seen so far that the sampler itself extends: a third and fourth family of generation graphs (`proc_gen_graphs`,
+`row_proc_gen_graphs`).  With both at their defaults generate takes the graphs above, unchanged.
 """
 import torch
 
@@ -80,6 +84,8 @@ class GraphedDecoder:
         self.gen_graphs = {}  # (bucket bound, greedy) -> (graph, logits): step + sampler (generate)
         self.row_graphs = {}  # per-row mode (attention_mask): bucket bound -> (graph, logits), reading pos_rows / len_rows
         self.row_gen_graphs = {}  # per-row mode: (bucket bound, greedy) -> (graph, logits)
+        self.proc_gen_graphs = {}  # with the logit processors (repetition_penalty / min_new_tokens): keyed as gen_graphs
+        self.row_proc_gen_graphs = {}  # ... and as row_gen_graphs
         self._gen = None  # generate's device words (allocated by its first call)
         self.position = 0
         self.positions = None  # per-row mode: the host's position of every row (None: one shared position)
@@ -208,12 +214,12 @@ class GraphedDecoder:
             self.positions[r] -= n
         self.seek_rows(self.positions)
 
-    def _advance(self, greedy=None):
+    def _advance(self, greedy=None, proc=False):
         """What `step` and `replay` share: roll a full window, pick (or capture) the bucket's graph, replay it on the decoder's stream
         between the caller's work, advance the position on the host as the graph did on the device.  greedy = True / False:
-        the generation graph (step + sampler) instead of the step graph."""
+        the generation graph (step + sampler) instead of the step graph; proc: the one whose sampler runs the logit processors."""
         if self.positions is not None:
-            return self._advance_rows(greedy)
+            return self._advance_rows(greedy, proc)
         if self.position + 1 > self.max_seq_len:  # past the window: forget the oldest positions (eagerly)
             live = [b.attn.cache.roll_kv_n_steps(self.position, n=StepPlan.ROLL) for b in self.blocks][0]
             self.seek(live)
@@ -222,9 +228,10 @@ class GraphedDecoder:
             graph, logits = self.graphs.get(bound) or self._capture(bound)
         else:
             key = (bound, bool(greedy))
-            if key not in self.gen_graphs:
-                self.gen_graphs[key] = self._capture(bound, sample=lambda lg: self._sample(lg, greedy))
-            graph, logits = self.gen_graphs[key]
+            family = self.proc_gen_graphs if proc else self.gen_graphs
+            if key not in family:
+                family[key] = self._capture(bound, sample=lambda lg: self._sample(lg, greedy, proc))
+            graph, logits = family[key]
         caller = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(caller)   # the ids were copied on the caller's stream
         with torch.cuda.stream(self.stream):
@@ -234,7 +241,7 @@ class GraphedDecoder:
         self._sync_host_state()
         return logits
 
-    def _advance_rows(self, greedy=None):
+    def _advance_rows(self, greedy=None, proc=False):
         """`_advance` in per-row mode: per-row rolls, the bucket of the largest position, the per-row graphs."""
         self._roll_rows()
         bound = self.bucket(max(self.positions) + 1)
@@ -242,9 +249,10 @@ class GraphedDecoder:
             graph, logits = self.row_graphs.get(bound) or self._capture(bound, rows=True)
         else:
             key = (bound, bool(greedy))
-            if key not in self.row_gen_graphs:
-                self.row_gen_graphs[key] = self._capture(bound, sample=lambda lg: self._sample(lg, greedy), rows=True)
-            graph, logits = self.row_gen_graphs[key]
+            family = self.row_proc_gen_graphs if proc else self.row_gen_graphs
+            if key not in family:
+                family[key] = self._capture(bound, sample=lambda lg: self._sample(lg, greedy, proc), rows=True)
+            graph, logits = family[key]
         caller = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(caller)
         with torch.cuda.stream(self.stream):
@@ -270,7 +278,8 @@ class GraphedDecoder:
     # ---- generation: sampler in the graph ---------------------------------------------------------------------------------
     def _gen_state(self, vocab, cap):
         """The device words generate owns.  Their addresses are baked into the generation graphs: reallocated (and the graphs
-        dropped) only when the vocabulary or the ring capacity has to grow."""
+        dropped) only when the vocabulary or the ring capacity has to grow.  history: the ids seen per row (bit v % 32 of word
+        v / 32), proc: struct AwqSampleProc -- the logit processors' state."""
         g = self._gen
         if g is not None and g["vocab"] == vocab and g["ring"].shape[1] >= cap:
             return g
@@ -282,16 +291,21 @@ class GraphedDecoder:
                  "ring": torch.zeros((self.batch, max(int(cap), 256)), dtype=torch.int32, device=dev),
                  "finished": torch.zeros(self.batch, dtype=torch.int32, device=dev),
                  "status": torch.zeros((self.batch + 31) // 32, dtype=torch.int32, device=dev),
-                 "ws": torch.zeros(ops.sample_workspace_bytes(self.batch, vocab), dtype=torch.uint8, device=dev)}
+                 "ws": torch.zeros(ops.sample_workspace_bytes(self.batch, vocab), dtype=torch.uint8, device=dev),
+                 "history": torch.zeros((self.batch, ops.sample_history_words(vocab)), dtype=torch.int32, device=dev),
+                 "proc": torch.zeros(16, dtype=torch.uint8, device=dev)}
         self.gen_graphs = {}
         self.row_gen_graphs = {}
+        self.proc_gen_graphs = {}
+        self.row_proc_gen_graphs = {}
         self._gen = g
         return g
 
-    def _sample(self, logits, greedy):
+    def _sample(self, logits, greedy, proc=False):
         g = self._gen
         ops.sample_launch(logits, g["params"], g["t"], self.tok.view(-1), g["status"], g["ws"], ring=g["ring"],
-                          finished=g["finished"], greedy=greedy)
+                          finished=g["finished"], greedy=greedy, proc=g["proc"] if proc else None,
+                          history=g["history"] if proc else None)
 
     def _check(self, g):
         st = g["status"].cpu()
@@ -302,7 +316,8 @@ class GraphedDecoder:
 
     @torch.inference_mode()
     def generate(self, input_ids, max_new_tokens, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
-                 eos_token_id=None, pad_token_id=None, check_every=16, attention_mask=None):
+                 eos_token_id=None, pad_token_id=None, check_every=16, attention_mask=None, repetition_penalty=1.0,
+                 min_new_tokens=0):
         """input_ids [batch, prompt] -> [batch, prompt + n] int64 on the device, n <= max_new_tokens; rows that emitted an EOS id
         are padded with pad_token_id (default: the first EOS id) from then on, and the run stops once every row has (HF's
         `generate` semantics).  The prompt is prefilled eagerly and token 1 sampled eagerly from its last position; every later
@@ -311,7 +326,11 @@ class GraphedDecoder:
         Gumbel-max draw with Philox numbers keyed by (seed, token index, row).
         attention_mask [batch, prompt] (0 / 1, see `prefill`): prompts of different lengths; row b's first token is sampled
         from its logits at its last real position and every row then advances at its own position.  The result is still
-        cat([input_ids, new], 1): for left-padded input, the layout transformers' `generate` returns."""
+        cat([input_ids, new], 1): for left-padded input, the layout transformers' `generate` returns.
+        repetition_penalty (> 0, 1 = off) and min_new_tokens (>= 0, 0 = off): transformers' RepetitionPenaltyLogitsProcessor and
+        MinNewTokensLengthLogitsProcessor, applied inside the sampler (ops.sample_tokens).  The penalty covers every id of
+        input_ids as passed (pad columns included, as transformers' input_ids carry them) and every generated token (pads of
+        finished rows included), also after a window roll has dropped their cache rows."""
         input_ids = input_ids.to(self.device)
         if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
             raise ValueError(f"input_ids must be [{self.batch}, prompt], got {tuple(input_ids.shape)}")
@@ -321,6 +340,8 @@ class GraphedDecoder:
         eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
         params = ops.sample_params(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, eos_ids=eos,
                                    pad=pad_token_id)
+        proc_bytes = ops.sample_proc_params(repetition_penalty, min_new_tokens)
+        proc = float(repetition_penalty) != 1.0 or int(min_new_tokens) > 0
         greedy = not do_sample or float(temperature) <= 0
         ragged = self._ragged(input_ids, attention_mask)
         logits = self.prefill(input_ids, attention_mask if ragged is not None else None)
@@ -334,12 +355,16 @@ class GraphedDecoder:
         g["ring"].zero_()
         g["finished"].zero_()
         g["status"].zero_()
-        self._sample(logits, greedy)  # token 1, eagerly, into self.tok
+        if proc:
+            g["proc"].copy_(proc_bytes)
+            g["history"].zero_()
+            ops.sample_history(input_ids, g["vocab"], out=g["history"])
+        self._sample(logits, greedy, proc)  # token 1, eagerly, into self.tok
         n = 1
         while n < max_new_tokens:
             if n % check_every == 0 and self._check(g):
                 break
-            self._advance(greedy=greedy)  # step on token n, sample token n + 1
+            self._advance(greedy=greedy, proc=proc)  # step on token n, sample token n + 1
             n += 1
         done = self._check(g)
         new = g["ring"][:, :n]

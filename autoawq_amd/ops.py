@@ -4,6 +4,7 @@ PyTorch is plumbing here (device memory, current stream); every computation is a
 gfx950 kernel reached through the C ABI of include/awq_hip.h.
 """
 import ctypes
+import math
 
 import torch
 
@@ -937,6 +938,56 @@ def sample_params(*, do_sample, temperature=1.0, top_k=0, top_p=1.0, seed=0, eos
     return torch.frombuffer(bytearray(bytes(p)), dtype=torch.uint8)
 
 
+def sample_proc_params(repetition_penalty=1.0, min_new_tokens=0):
+    """Validate the logit processors and pack them as struct AwqSampleProc: a 16-byte CPU uint8 tensor the caller copies to the
+    device.  repetition_penalty finite and > 0 (1 = off), min_new_tokens >= 0 (0 = off) -- transformers' checks."""
+    p = float(repetition_penalty)
+    if not math.isfinite(p) or p <= 0.0:
+        raise ValueError(f"repetition_penalty has to be a strictly positive float, got {repetition_penalty}")
+    if isinstance(min_new_tokens, bool) or int(min_new_tokens) != min_new_tokens or int(min_new_tokens) < 0:
+        raise ValueError(f"min_new_tokens has to be a non-negative integer, got {min_new_tokens}")
+    q = _lib.AwqSampleProc()
+    q.repetition_penalty = p
+    q.min_new_tokens = min(int(min_new_tokens), 0x7FFFFFFF)
+    return torch.frombuffer(bytearray(bytes(q)), dtype=torch.uint8)
+
+
+def sample_history_words(vocab):
+    """int32 words per row of a sampler history: bit v % 32 of word v / 32 = token v seen"""
+    return (int(vocab) + 31) // 32
+
+
+def sample_history(ids, vocab, out=None):
+    """OR the ids [B, S] (or [S]: one row; int64, on the device) into a history: int32 [B, >= ceil(vocab / 32)] on the device,
+    bit v % 32 of word v / 32 set for every id v of row b.  out=None: a new zeroed history; otherwise `out` is extended in place
+    (its earlier bits stay).  Ids outside [0, vocab) are refused (this waits for the device once to check them)."""
+    V = int(vocab)
+    if not 1 <= V <= 1 << 20:
+        raise ValueError(f"sample_history: vocab must be in [1, 2^20], got {vocab}")
+    if not isinstance(ids, torch.Tensor) or ids.dim() not in (1, 2) or ids.dtype not in (torch.int64, torch.int32):
+        raise ValueError("sample_history: ids must be an int64 [B, S] tensor")
+    ids2 = ids.view(1, -1) if ids.dim() == 1 else ids
+    B, S = ids2.shape
+    if ids2.numel() and bool(((ids2 < 0) | (ids2 >= V)).any()):
+        raise ValueError(f"sample_history: ids outside [0, {V})")
+    if out is None:
+        _require_gpu(ids2)
+        with torch.inference_mode(False):
+            out = torch.zeros((B, sample_history_words(V)), dtype=torch.int32, device=ids2.device)
+    if out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < sample_history_words(V) or out.stride(1) != 1:
+        raise ValueError(f"sample_history: out must be int32 [{B}, >= {sample_history_words(V)}] with unit column stride")
+    _require_gpu(ids2, out)
+    if B == 0 or S == 0:
+        return out
+    ids2 = ids2.long()
+    if ids2.stride(1) != 1:
+        ids2 = ids2.contiguous()
+    with torch.cuda.device(out.device):
+        rc = _lib.lib().awq_sample_history_seed(_ptr(out), out.stride(0), _ptr(ids2), ids2.stride(0), B, S, V, _stream())
+    _lib.check(rc, "awq_sample_history_seed")
+    return out
+
+
 def sample_workspace_bytes(B, V):
     return int(_lib.lib().awq_sample_workspace_bytes(B, V))
 
@@ -963,13 +1014,22 @@ def _logits_rows(logits):
     return rows, rows.stride(0)
 
 
-def sample_launch(logits, params, t, out, status, workspace, ring=None, finished=None, greedy=False):
+def sample_launch(logits, params, t, out, status, workspace, ring=None, finished=None, greedy=False, proc=None, history=None):
     """The raw launch (no validation of the configuration, no sync): every buffer a device tensor the caller owns --
     params (64 bytes, sample_params), t (int32 [1]), out (int64, one element per row, any row stride), status (int32,
-    ceil(B / 32) words), workspace (zeroed once), ring (int32 [B, cap]) and finished (int32 [B]) optional.  Capturable."""
+    ceil(B / 32) words), workspace (zeroed once), ring (int32 [B, cap]) and finished (int32 [B]) optional.  proc (16 bytes,
+    sample_proc_params) with history (int32 [B, >= ceil(V / 32)], sample_history): the logit processors, and the emitted
+    tokens ORed into the history (awq_sample_tokens_ex).  Capturable."""
     rows, rs = _logits_rows(logits)
     B, V = rows.shape
-    _require_gpu(rows, params, t, out, status, workspace, ring, finished)
+    _require_gpu(rows, params, t, out, status, workspace, ring, finished, proc, history)
+    if (proc is None) != (history is None):
+        raise _lib.AwqHipError("sample_launch: proc and history go together")
+    if history is not None and (history.dtype != torch.int32 or history.dim() != 2 or history.shape[0] != B
+                                or history.shape[1] < sample_history_words(V) or history.stride(1) != 1):
+        raise _lib.AwqHipError(f"sample_launch: history must be int32 [{B}, >= {sample_history_words(V)}] with unit column stride")
+    if proc is not None and (proc.numel() * proc.element_size() < ctypes.sizeof(_lib.AwqSampleProc)):
+        raise _lib.AwqHipError("sample_launch: proc must hold 16 bytes (sample_proc_params)")
     if out.numel() < B or status.numel() * 32 < B or (finished is not None and finished.numel() < B):
         raise _lib.AwqHipError("sample_launch: out / status / finished too small for the batch")
     if ring is not None and (ring.dim() != 2 or ring.shape[0] != B or not ring.is_contiguous() or ring.dtype != torch.int32):
@@ -987,20 +1047,35 @@ def sample_launch(logits, params, t, out, status, workspace, ring=None, finished
     a.workspace, a.workspace_bytes = _ptr(workspace), workspace.numel()
     with torch.cuda.device(rows.device):
         a.stream = _stream()
-        rc = _lib.lib().awq_sample_tokens(ctypes.byref(a))
-    _lib.check(rc, "awq_sample_tokens")
+        if proc is None:
+            rc = _lib.lib().awq_sample_tokens(ctypes.byref(a))
+        else:
+            q = _lib.AwqSampleProcArgs()
+            q.struct_bytes = ctypes.sizeof(_lib.AwqSampleProcArgs)
+            q.flags = 0
+            q.proc, q.history, q.history_stride = _ptr(proc), _ptr(history), history.stride(0)
+            rc = _lib.lib().awq_sample_tokens_ex(ctypes.byref(a), ctypes.byref(q))
+    _lib.check(rc, "awq_sample_tokens" if proc is None else "awq_sample_tokens_ex")
     return out
 
 
 def sample_tokens(logits, *, do_sample, temperature=1.0, top_k=0, top_p=1.0, seed=0, t=1, eos_ids=(), pad=None, out=None,
-                  ring=None, finished=None, status=None):
+                  ring=None, finished=None, status=None, repetition_penalty=1.0, min_new_tokens=0, history=None):
     """One token per row of fp16 logits [B, V] (or the last position of [B, T, V]), chosen on the device by
     csrc/sample.hip: greedy argmax (ties to the lowest index), or temperature -> top-k -> top-p -> Gumbel-max draw with
     Philox4x64-10 numbers keyed by (seed, t, row).  t is the 1-based index of the generated token (an int, or an int32 [1]
     device word the launch advances by one).  Returns out (int64 [B]).  ring (int32 [B, cap]) receives the token at column
     t - 1; finished (int32 [B]) latches on an EOS id, after which the row emits pad.  Without `status` the call waits for
     the result and raises AwqHipError if a row held NaN / +inf or kept nothing; with an int32 status tensor the bits are
-    left there (sticky) and the call does not synchronise."""
+    left there (sticky) and the call does not synchronise.
+    Logit processors (transformers' order, before the warpers, greedy too): while t <= min_new_tokens the EOS ids are -inf;
+    logits of the ids set in `history` (int32 [B, >= ceil(V / 32)], sample_history) are divided by repetition_penalty (positive
+    ones) or multiplied by it (negative ones), then rounded to fp16.  With a history the emitted tokens are ORed into it in
+    place, so a loop of calls behaves like transformers' `input_ids`.  A penalty other than 1 needs a history."""
+    proc = sample_proc_params(repetition_penalty, min_new_tokens)
+    if float(repetition_penalty) != 1.0 and history is None:
+        raise ValueError("sample_tokens: repetition_penalty needs a history of the ids seen (sample_history)")
+    use_proc = history is not None or int(min_new_tokens) > 0
     params = sample_params(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, eos_ids=eos_ids,
                            pad=pad)
     if not isinstance(t, torch.Tensor) and int(t) < 1:
@@ -1023,7 +1098,12 @@ def sample_tokens(logits, *, do_sample, temperature=1.0, top_k=0, top_p=1.0, see
         if own_status:
             status = torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev)
         ws = _sample_workspace(dev, need)
-        sample_launch(rows, params_d, t_d, out, status, ws, ring=ring, finished=finished, greedy=not do_sample or temperature <= 0)
+        proc_d = hist = None
+        if use_proc:
+            proc_d = proc.to(dev, non_blocking=False)
+            hist = history if history is not None else torch.zeros((B, sample_history_words(V)), dtype=torch.int32, device=dev)
+        sample_launch(rows, params_d, t_d, out, status, ws, ring=ring, finished=finished, greedy=not do_sample or temperature <= 0,
+                      proc=proc_d, history=hist)
         if own_status:
             bad = [r for r in range(B) if (int(status[r // 32].item()) >> (r % 32)) & 1] if bool(status.any()) else []
             if bad:

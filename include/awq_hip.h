@@ -563,6 +563,40 @@ typedef struct AwqSampleArgs {
 AWQ_EXPORT size_t awq_sample_workspace_bytes(int64_t B, int64_t V);
 AWQ_EXPORT int awq_sample_tokens(const AwqSampleArgs* args);
 
+/* ---- logit processors of the sampler: repetition penalty and min_new_tokens (transformers' RepetitionPenaltyLogitsProcessor
+ * and MinNewTokensLengthLogitsProcessor, which `generate` applies before the warpers, greedy included) -----------------------
+ * awq_sample_tokens_ex(args, proc) is awq_sample_tokens with every pass, and the greedy argmax, reading the PROCESSED value of
+ * each logit instead of the logit; proc == NULL is exactly awq_sample_tokens.  For row r at token index t (the *t word, read at
+ * block start) the logit i with fp16 bits h becomes:
+ *   1. -inf if t <= min_new_tokens and i is one of the n_eos EOS ids of AwqSampleParams (t - 1 tokens are new so far);
+ *   2. otherwise, if bit i of history row r is set and h is finite: v = float(h); v = v < 0 ? v * p : v / p in fp32 (correctly
+ *      rounded division), then v rounded to fp16 (nearest even) saturating to +-65504 -- a finite logit stays finite, +-0 keep
+ *      their sign; -inf, +inf and NaN pass unchanged, so the status rules are those of awq_sample_tokens.
+ * The processed value is fp16(transformers' fp32 value) wherever that is in range: tokens equal transformers' on rows where no
+ * two candidates collide after this rounding (the same caveat as the top-p tie rule).  In the same launch, after every block of
+ * the row has read it, the bit of the token written to out[row] is set in history row r (also the pad of a finished or failed
+ * row; a pad outside [0, V) sets nothing).  AwqSampleProc lives in DEVICE memory, as AwqSampleParams does, so one captured
+ * launch serves every penalty.  history: uint32 [B, history_stride] words, bit v % 32 of word v / 32 = token v seen;
+ * history_stride >= ceil(V / 32).  awq_sample_history_seed ORs the ids [B, S] (int64, ids_stride elements between rows) into a
+ * history; ids outside [0, V) are ignored. */
+typedef struct AwqSampleProc {
+    float repetition_penalty; /* finite, > 0; 1 = off */
+    int32_t min_new_tokens;   /* >= 0; 0 = off */
+    int32_t pad[2];
+} AwqSampleProc;
+
+typedef struct AwqSampleProcArgs {
+    uint32_t struct_bytes; /* sizeof(AwqSampleProcArgs) */
+    uint32_t flags;        /* 0 (reserved) */
+    const AwqSampleProc* proc;
+    uint32_t* history;     /* [B, history_stride] */
+    int64_t history_stride; /* words */
+} AwqSampleProcArgs;
+
+AWQ_EXPORT int awq_sample_tokens_ex(const AwqSampleArgs* args, const AwqSampleProcArgs* proc);
+AWQ_EXPORT int awq_sample_history_seed(uint32_t* history, int64_t history_stride, const int64_t* ids, int64_t ids_stride,
+                                       int64_t B, int64_t S, int64_t V, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ sampler captured into the decode graph, the host looking at the flags every 16 t
 (dec.step + torch.argmax + a per-token .item() EOS check), at several contexts and batch sizes.  Decode tok/s excludes the
 prompt's prefill (timed on its own and subtracted).  --ragged: prompts of different lengths (attention_mask) in one generate
 call, against the same prompts one at a time and a uniform batch padded to the longest prompt.  --sampler-only times the sampler alone (run it under
-`rocprofv3 --kernel-trace --stats` for per-kernel durations)."""
+`rocprofv3 --kernel-trace --stats` for per-kernel durations).  --repetition-penalty / --min-new-tokens add legs with the
+sampler's logit processors beside the default ones (in --sampler-only, a history pre-seeded with 2048 ids)."""
 import argparse, json, os, sys, time
 import torch
 
@@ -21,7 +22,11 @@ def _timed(fn):
     return time.perf_counter() - t0, r
 
 
-def bench_generate(layers=32, contexts=(64, 2048), batches=(1, 4), new=128):
+def _proc_tag(rp, mnt):
+    return f" rp={rp:g} mnt={mnt}"
+
+
+def bench_generate(layers=32, contexts=(64, 2048), batches=(1, 4), new=128, rp=1.0, mnt=0):
     import bench_decode_model
     from autoawq_amd.modules.fused.decode import GraphedDecoder
 
@@ -47,6 +52,11 @@ def bench_generate(layers=32, contexts=(64, 2048), batches=(1, 4), new=128):
 
             cfgs = [("hand greedy", hand), ("generate greedy", lambda: dec.generate(prompt, new)),
                     ("generate top_k=50 top_p=0.9", lambda: dec.generate(prompt, new, do_sample=True, top_k=50, top_p=0.9, seed=1))]
+            if rp != 1.0 or mnt:
+                proc = {"repetition_penalty": rp, "min_new_tokens": mnt}
+                cfgs += [("generate greedy" + _proc_tag(rp, mnt), lambda: dec.generate(prompt, new, **proc)),
+                         ("generate top_k=50 top_p=0.9" + _proc_tag(rp, mnt),
+                          lambda: dec.generate(prompt, new, do_sample=True, top_k=50, top_p=0.9, seed=1, **proc))]
             for name, fn in cfgs:
                 fn()  # captures
                 t = min(_timed(fn)[0] for _ in range(2))
@@ -109,7 +119,7 @@ def bench_ragged(layers=32, batches=(4, 8), new=128, shortest=64, longest=2048):
     return rows
 
 
-def bench_sampler(vocabs=(32000, 128256, 152064), batches=(1, 4), calls=200):
+def bench_sampler(vocabs=(32000, 128256, 152064), batches=(1, 4), calls=200, rp=1.0, mnt=0):
     from autoawq_amd import ops
 
     dev = torch.device("cuda")
@@ -121,11 +131,18 @@ def bench_sampler(vocabs=(32000, 128256, 152064), batches=(1, 4), calls=200):
             out = torch.empty(B, dtype=torch.int64, device=dev)
             status = torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev)
             ws = torch.zeros(ops.sample_workspace_bytes(B, V), dtype=torch.uint8, device=dev)
-            for name, greedy, cfg in (("greedy", True, {"do_sample": False}),
-                                      ("top_k=50 top_p=0.9", False, {"do_sample": True, "top_k": 50, "top_p": 0.9, "seed": 1}),
-                                      ("top_p=0.9", False, {"do_sample": True, "top_p": 0.9, "seed": 1})):
-                params = ops.sample_params(**cfg).to(dev)
-                launch = lambda: ops.sample_launch(x, params, t, out, status, ws, greedy=greedy)
+            legs = [(False, "greedy", True, {"do_sample": False}),
+                    (False, "top_k=50 top_p=0.9", False, {"do_sample": True, "top_k": 50, "top_p": 0.9, "seed": 1}),
+                    (False, "top_p=0.9", False, {"do_sample": True, "top_p": 0.9, "seed": 1})]
+            if rp != 1.0 or mnt:
+                legs += [(True, name + _proc_tag(rp, mnt), greedy, cfg) for _, name, greedy, cfg in legs]
+            for proc_on, name, greedy, cfg in legs:
+                params = ops.sample_params(eos_ids=[V - 1] if proc_on else (), **cfg).to(dev)
+                proc = hist = None
+                if proc_on:  # the history of a 2048-token context
+                    proc = ops.sample_proc_params(rp, mnt).to(dev)
+                    hist = ops.sample_history(torch.randint(0, V, (B, 2048), device=dev), V)
+                launch = lambda: ops.sample_launch(x, params, t, out, status, ws, greedy=greedy, proc=proc, history=hist)
                 s = torch.cuda.Stream()
                 with torch.cuda.stream(s):
                     launch()
@@ -156,10 +173,12 @@ if __name__ == "__main__":
     ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--new", type=int, default=128)
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--min-new-tokens", type=int, default=0)
     a = ap.parse_args()
     if a.sampler_only:
-        bench_sampler()
+        bench_sampler(rp=a.repetition_penalty, mnt=a.min_new_tokens)
     elif a.ragged:
         bench_ragged(layers=a.layers, new=a.new)
     else:
-        bench_generate(layers=a.layers, new=a.new)
+        bench_generate(layers=a.layers, new=a.new, rp=a.repetition_penalty, mnt=a.min_new_tokens)
