@@ -15,9 +15,10 @@ names it and `by_layout` times the same step on WQLinear_GEMM and WQLinear_GEMVF
 model tensor-parallel over N GPUs (column-split qkv / gate+up, row-split o / down with one RCCL all-reduce each)
 -- strong scaling; `--model 70b` = BASELINE configs[3].
 
-Secondary objects on the same JSON line (N = 1, never `value`; each guarded so that the headline cannot
-depend on them): `sustained` (the same graph for >= 1 s), `per_shape` (the four Linear shapes of the headline one by
-one, each with its own roofline), `by_layout`, `gemm_bs` (configs[2]'s "bs=8 GEMM for 4096x11008": M = 1 .. 64, cold
+A plain run does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.
+`--full` adds secondary objects to the same JSON line (N = 1, never `value`; each measured after the timed steps and guarded
+so that the headline cannot depend on them): `sustained` (the same graph for >= 1 s), `per_shape` (the four Linear shapes
+of the headline one by one, each with its own roofline), `by_layout`, `gemm_bs` (configs[2]'s "bs=8 GEMM for 4096x11008": M = 1 .. 64, cold
 weights, GEMM and GEMV layouts), `gemm_prefill` (configs[2]: M = 8 x 2048 = 16384, fused MFMA kernel vs HIP dequant
 + vendor GEMM, which one the module picks), `moe_bs4` (configs[4]), `decode_independent` (the headline's Linears with FIXED inputs: rounds 1-5's headline; since round 6 the headline itself has the TRUE
 data dependencies: each consumes the previous one's output), `whole_model` (the fused decoder), and `cpu_baseline`
@@ -728,9 +729,13 @@ def main():
                     help="checkpoint format of the Linears: WQLinear_GEMV (default: the reference's own batch-1 format, README.md:96-97) / "
                          "WQLinear_GEMM / WQLinear_GEMVFast buffers")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-whole-model", action="store_true", help="skip the secondary whole-decoder figure")
-    ap.add_argument("--no-secondary", action="store_true", help="headline leg (and cpu_baseline) only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the secondary objects (sustained, per_shape, decode_independent, by_layout, "
+                         "gemm_bs, gemm_prefill, prefill_attention, moe_bs4, moe_prefill, whole_model) and cpu_baseline; a plain run "
+                         "measures the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-whole-model", action="store_true", help="with --full: skip the secondary whole-decoder figure")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: headline leg (and cpu_baseline) only")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: the multi-rank plumbing only (rendezvous over gloo, per-rank shard shapes, the collective's rank-"
                          "consistent fallback, barrier + max-over-ranks timing) with launches replaced by zero outputs; prints a line "
@@ -822,7 +827,7 @@ def main():
             oneshot.check()  # a rank that gave up on a peer wrote NaN and raised the sticky word: the timing would be meaningless
         last_outs = [o.cpu() for o in outs] if a.dump_outputs and rank == 0 else None  # before any later replay (sustained) runs
         sustained = None
-        if world == 1 and not a.no_secondary:  # the same replay for >= 1 s: a leg the GPU-busy sampler of the driver can see
+        if world == 1 and a.full and not a.no_secondary:  # `sustained`: the same replay for >= 1 s
             t_end, n_sus = time.perf_counter() + 1.2, 0
             s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s0.record(stream)
@@ -894,8 +899,8 @@ def main():
             ms_s, n_s = sustained
             out["sustained"] = {"seconds": ms_s / 1e3, "steps": n_s, "ms_per_step": ms_s / n_s, "tok_s": 1000.0 * n_s / ms_s,
                                 "GBps": bytes_step * n_s / ms_s / 1e6, "frac": bytes_step * n_s / ms_s / 1e6 / HBM_PEAK_GBS}
-        full = world == 1 and layers == cfg["layers"] and a.model == "7b" and not a.no_secondary
-        if full:
+        secondary = a.full and world == 1 and layers == cfg["layers"] and a.model == "7b" and not a.no_secondary
+        if secondary:
             del graph, outs
             legs = [("per_shape", lambda: leg_per_shape(dev, ops, model, shapes)),
                     ("decode_independent", lambda: leg_decode_independent(dev, ops, model, bytes_step)),
@@ -911,7 +916,7 @@ def main():
                 except Exception as e:  # the headline line must not depend on a secondary leg
                     out[name] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
                 torch.cuda.empty_cache()
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg["layers"])
         print(json.dumps(out), flush=True)
     if dist is not None:

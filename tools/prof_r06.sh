@@ -12,9 +12,9 @@ mkdir -p $O/bin
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -o $O/bin/stream_probe2 tools/stream_probe2.hip > $O/r06_probe_build.log 2>&1
 if [ "$2" != "quick" ]; then
 rm -rf $O/prof_r06
-rocprofv3 --kernel-trace --stats -d $O/prof_r06 -o bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/r06_prof_bench.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/prof_r06 -o bench -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/r06_prof_bench.log 2>&1
 DB=$(find $O/prof_r06 -name "*.db" | head -1)
-{ echo "# git head $HEAD; kernel source fingerprint: $FP"; echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline   (tools/prof_r06.sh; every leg of bench.py)"; echo "# bench line of this profiled run:"; grep '^{"metric' $O/r06_prof_bench.log | cut -c1-400; python tools/rocpd_summary.py $DB; } > $O/r06_bench_kernel_trace_stats.txt 2>&1
+{ echo "# git head $HEAD; kernel source fingerprint: $FP"; echo "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline   (tools/prof_r06.sh; every leg of bench.py)"; echo "# bench line of this profiled run:"; grep '^{"metric' $O/r06_prof_bench.log | cut -c1-400; python tools/rocpd_summary.py $DB; } > $O/r06_bench_kernel_trace_stats.txt 2>&1
 rm -rf $O/prof_r06
 rocprofv3 --kernel-trace --stats -d $O/prof_r06 -o bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $O/r06_prof_bench_headline.log 2>&1
 DB=$(find $O/prof_r06 -name "*.db" | head -1)
