@@ -96,6 +96,15 @@ SIGNATURES = {
     "awq_rope_kv_append_rows": (c_int, [c_void_p] * 7 + [c_int64] * 7 + [c_void_p]),
     "awq_decode_attention_rows": (c_int, [c_void_p] * 5 + [c_int64] * 6 + [c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "awq_decode_attention_rope_rows": (c_int, [c_void_p] * 7 + [c_int64] * 6 + [c_float, c_void_p, c_size_t, c_void_p]),
+    "awq_rope_kv_append_fp8": (c_int, [c_void_p] * 9 + [c_int64] * 8 + [c_void_p]),
+    "awq_rope_kv_append_rows_fp8": (c_int, [c_void_p] * 9 + [c_int64] * 7 + [c_void_p]),
+    "awq_decode_attention_fp8": (c_int, [c_void_p] * 7 + [c_int64] * 7 + [c_float, c_void_p, c_size_t, c_void_p]),
+    "awq_decode_attention_ex_fp8": (c_int, [c_void_p] * 7 + [c_int64] * 7 + [c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "awq_decode_attention_rope_fp8": (c_int, [c_void_p] * 9 + [c_int64] * 7 + [c_float, c_void_p, c_size_t, c_void_p]),
+    "awq_decode_attention_rows_fp8": (c_int, [c_void_p] * 7 + [c_int64] * 6 + [c_float, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "awq_decode_attention_rope_rows_fp8": (c_int, [c_void_p] * 9 + [c_int64] * 6 + [c_float, c_void_p, c_size_t, c_void_p]),
+    "awq_kv_quant_fp8": (c_int, [c_void_p] * 3 + [c_int64] * 6 + [c_void_p]),
+    "awq_kv_dequant_fp8": (c_int, [c_void_p] * 3 + [c_int64] * 5 + [c_void_p]),
     "awq_moe_route": (c_int, [c_void_p] * 6 + [c_int64, c_int64, c_int64, c_int, c_int64, c_void_p]),
     "awq_moe_route_local": (c_int, [c_void_p] * 6 + [c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int64, c_void_p]),
     "awq_grouped_gemm_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),

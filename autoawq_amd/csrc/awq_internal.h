@@ -163,10 +163,16 @@ int awq_launch_rmsnorm(const uint16_t* x, uint16_t* residual, const uint16_t* w,
                        float eps, hipStream_t st);
 int awq_launch_rope_kv_append(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, const float* cos_t,
                               const float* sin_t, const int32_t* pos_dev, int start_pos, int B, int S, int Hq, int Hkv, int D,
-                              int rot, int Tmax, hipStream_t st, bool rows = false);
+                              int rot, int Tmax, hipStream_t st, bool rows = false, float* k_scale = nullptr,
+                              float* v_scale = nullptr);
 size_t awq_decode_attention_workspace_bytes_impl(int B, int Hq, int max_splits);
 int awq_launch_decode_attention(const uint16_t* q, uint16_t* k_cache, uint16_t* v_cache, uint16_t* out,
                                 const int32_t* len_dev, int seq_len, int max_len, int B, int Hq, int Hkv, int D, int Tmax,
                                 float scale, void* workspace, size_t workspace_bytes, const float* cos_t,
                                 const float* sin_t, hipStream_t st, float softcap = 0.f, const float* alibi_slopes = nullptr,
-                                bool rows = false);
+                                bool rows = false, float* k_scale = nullptr, float* v_scale = nullptr);
+// fp8 KV cache (k_scale / v_scale above non-NULL: the caches hold e4m3 codes): fp16 rows <-> codes + scales
+int awq_launch_kv_quant_fp8(const uint16_t* x, uint8_t* codes, float* scales, int B, int S, int Hkv, int Tmax, int start,
+                            hipStream_t st);
+int awq_launch_kv_dequant_fp8(const uint8_t* codes, const float* scales, uint16_t* out, int B, int n, int Hkv, int Tmax,
+                              hipStream_t st);

@@ -740,3 +740,139 @@ int awq_decode_attention_rope_rows(const uint16_t* qkv, uint16_t* k_cache, uint1
                                        (int)n_kv_heads, (int)head_dim, (int)max_seq, scale, workspace, workspace_bytes,
                                        cos_table, sin_table, static_cast<hipStream_t>(stream), 0.f, nullptr, true);
 }
+
+// ---- fp8 KV cache (decoder.hip, KV8): same checks as the fp16 entry points, plus head_dim == 128 and the scale arrays
+static int kv8_check(const void* kc, const void* vc, const float* ks, const float* vs, int64_t head_dim) {
+    if (!kc || !vc || !ks || !vs) return AWQ_ERR_NULL;
+    if (head_dim != 128) return AWQ_ERR_UNSUPPORTED;
+    if (!aligned16(kc) || !aligned16(vc) || (reinterpret_cast<uintptr_t>(ks) & 3) || (reinterpret_cast<uintptr_t>(vs) & 3))
+        return AWQ_ERR_BAD_ALIGNMENT;
+    return AWQ_OK;
+}
+
+int awq_rope_kv_append_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k_cache, uint8_t* v_cache, float* k_scale, float* v_scale,
+                           const float* cos_table, const float* sin_table, const int32_t* pos_dev, int64_t start_pos, int64_t B,
+                           int64_t S, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim, int64_t max_seq,
+                           void* stream) {
+    if (B < 0 || S < 0 || B * S > INT32_MAX / 1024 || max_seq < 1 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (B * S == 0) return AWQ_OK;
+    if (!qkv || !q_out || (rotary_dim > 0 && (!cos_table || !sin_table))) return AWQ_ERR_NULL;
+    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
+    return awq_launch_rope_kv_append(qkv, q_out, reinterpret_cast<uint16_t*>(k_cache), reinterpret_cast<uint16_t*>(v_cache),
+                                     cos_table, sin_table, pos_dev, (int)start_pos, (int)B, (int)S, (int)n_heads, (int)n_kv_heads,
+                                     (int)head_dim, (int)rotary_dim, (int)max_seq, static_cast<hipStream_t>(stream), false, k_scale,
+                                     v_scale);
+}
+
+int awq_rope_kv_append_rows_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k_cache, uint8_t* v_cache, float* k_scale,
+                                float* v_scale, const float* cos_table, const float* sin_table, const int32_t* pos_rows, int64_t B,
+                                int64_t S, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim,
+                                int64_t max_seq, void* stream) {
+    if (B < 0 || S < 0 || B * S > INT32_MAX / 1024 || max_seq < 1 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (B * S == 0) return AWQ_OK;
+    if (!qkv || !q_out || !pos_rows || (rotary_dim > 0 && (!cos_table || !sin_table))) return AWQ_ERR_NULL;
+    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
+    return awq_launch_rope_kv_append(qkv, q_out, reinterpret_cast<uint16_t*>(k_cache), reinterpret_cast<uint16_t*>(v_cache),
+                                     cos_table, sin_table, pos_rows, 0, (int)B, (int)S, (int)n_heads, (int)n_kv_heads, (int)head_dim,
+                                     (int)rotary_dim, (int)max_seq, static_cast<hipStream_t>(stream), true, k_scale, v_scale);
+}
+
+int awq_decode_attention_ex_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache, const float* k_scale,
+                                const float* v_scale, uint16_t* out, const int32_t* len_dev, int64_t seq_len, int64_t max_len,
+                                int64_t B, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale,
+                                float softcap, const float* alibi_slopes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (!(softcap >= 0.f)) return AWQ_ERR_BAD_SHAPE;
+    if (B == 0) return AWQ_OK;
+    if (!q || !out) return AWQ_ERR_NULL;
+    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
+    if (!aligned16(q) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
+    return awq_launch_decode_attention(q, reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(k_cache)),
+                                       reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(v_cache)), out, len_dev, (int)seq_len,
+                                       (int)max_len, (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_seq, scale,
+                                       workspace, workspace_bytes, nullptr, nullptr, static_cast<hipStream_t>(stream), softcap,
+                                       alibi_slopes, false, const_cast<float*>(k_scale), const_cast<float*>(v_scale));
+}
+
+int awq_decode_attention_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache, const float* k_scale,
+                             const float* v_scale, uint16_t* out, const int32_t* len_dev, int64_t seq_len, int64_t max_len, int64_t B,
+                             int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    return awq_decode_attention_ex_fp8(q, k_cache, v_cache, k_scale, v_scale, out, len_dev, seq_len, max_len, B, n_heads,
+                                       n_kv_heads, head_dim, max_seq, scale, 0.f, nullptr, workspace, workspace_bytes, stream);
+}
+
+int awq_decode_attention_rope_fp8(const uint16_t* qkv, uint8_t* k_cache, uint8_t* v_cache, float* k_scale, float* v_scale,
+                                  const float* cos_table, const float* sin_table, uint16_t* out, const int32_t* pos_dev,
+                                  int64_t start_pos, int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads,
+                                  int64_t head_dim, int64_t max_seq, float scale, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (B == 0) return AWQ_OK;
+    if (!qkv || !out || !cos_table || !sin_table) return AWQ_ERR_NULL;
+    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
+    if (!aligned16(qkv) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
+    if (!pos_dev && (start_pos < 0 || start_pos >= max_seq)) return AWQ_ERR_BAD_SHAPE;
+    return awq_launch_decode_attention(qkv, reinterpret_cast<uint16_t*>(k_cache), reinterpret_cast<uint16_t*>(v_cache), out, pos_dev,
+                                       (int)start_pos, (int)max_len, (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim,
+                                       (int)max_seq, scale, workspace, workspace_bytes, cos_table, sin_table,
+                                       static_cast<hipStream_t>(stream), 0.f, nullptr, false, k_scale, v_scale);
+}
+
+int awq_decode_attention_rows_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache, const float* k_scale,
+                                  const float* v_scale, uint16_t* out, const int32_t* len_rows, int64_t max_len, int64_t B,
+                                  int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, float softcap,
+                                  const float* alibi_slopes, void* workspace, size_t workspace_bytes, void* stream) {
+    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (!(softcap >= 0.f)) return AWQ_ERR_BAD_SHAPE;
+    if (B == 0) return AWQ_OK;
+    if (!q || !out || !len_rows) return AWQ_ERR_NULL;
+    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
+    if (!aligned16(q) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
+    return awq_launch_decode_attention(q, reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(k_cache)),
+                                       reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(v_cache)), out, len_rows, 1, (int)max_len,
+                                       (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_seq, scale, workspace,
+                                       workspace_bytes, nullptr, nullptr, static_cast<hipStream_t>(stream), softcap, alibi_slopes,
+                                       true, const_cast<float*>(k_scale), const_cast<float*>(v_scale));
+}
+
+int awq_decode_attention_rope_rows_fp8(const uint16_t* qkv, uint8_t* k_cache, uint8_t* v_cache, float* k_scale, float* v_scale,
+                                       const float* cos_table, const float* sin_table, uint16_t* out, const int32_t* pos_rows,
+                                       int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim,
+                                       int64_t max_seq, float scale, void* workspace, size_t workspace_bytes, void* stream) {
+    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (B == 0) return AWQ_OK;
+    if (!qkv || !out || !cos_table || !sin_table || !pos_rows) return AWQ_ERR_NULL;
+    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
+    if (!aligned16(qkv) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
+    return awq_launch_decode_attention(qkv, reinterpret_cast<uint16_t*>(k_cache), reinterpret_cast<uint16_t*>(v_cache), out, pos_rows, 0,
+                                       (int)max_len, (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_seq, scale,
+                                       workspace, workspace_bytes, cos_table, sin_table, static_cast<hipStream_t>(stream), 0.f, nullptr,
+                                       true, k_scale, v_scale);
+}
+
+int awq_kv_quant_fp8(const uint16_t* x, uint8_t* cache, float* scales, int64_t B, int64_t S, int64_t n_kv_heads, int64_t head_dim,
+                     int64_t max_seq, int64_t start_pos, void* stream) {
+    if (B < 0 || S < 0 || n_kv_heads < 1 || max_seq < 1 || max_seq > INT32_MAX || start_pos < 0 || start_pos + S > max_seq ||
+        B * max_seq * n_kv_heads > INT32_MAX * (int64_t)16)
+        return AWQ_ERR_BAD_SHAPE;
+    if (B * S == 0) return AWQ_OK;
+    if (!x) return AWQ_ERR_NULL;
+    if (int rc = kv8_check(cache, cache, scales, scales, head_dim)) return rc;
+    if (!aligned16(x)) return AWQ_ERR_BAD_ALIGNMENT;
+    return awq_launch_kv_quant_fp8(x, cache, scales, (int)B, (int)S, (int)n_kv_heads, (int)max_seq, (int)start_pos,
+                                   static_cast<hipStream_t>(stream));
+}
+
+int awq_kv_dequant_fp8(const uint8_t* cache, const float* scales, uint16_t* out, int64_t B, int64_t n, int64_t n_kv_heads,
+                       int64_t head_dim, int64_t max_seq, void* stream) {
+    if (B < 0 || n < 0 || n_kv_heads < 1 || max_seq < 1 || max_seq > INT32_MAX || n > max_seq ||
+        B * max_seq * n_kv_heads > INT32_MAX * (int64_t)16)
+        return AWQ_ERR_BAD_SHAPE;
+    if (B * n == 0) return AWQ_OK;
+    if (!out) return AWQ_ERR_NULL;
+    if (int rc = kv8_check(cache, cache, scales, scales, head_dim)) return rc;
+    if (!aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
+    return awq_launch_kv_dequant_fp8(cache, scales, out, (int)B, (int)n, (int)n_kv_heads, (int)max_seq,
+                                     static_cast<hipStream_t>(stream));
+}

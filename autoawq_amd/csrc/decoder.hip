@@ -9,6 +9,8 @@
 //   awq_decode_attention  flash_attn_with_kvcache(q, k_cache, v_cache, cache_seqlens, causal=True)  attn.py:291-302
 // (awq_ext / flash-attn sources are not in the reference tree: semantics from the call sites and
 // from the torch code around them.)
+#include <type_traits>
+
 #include "awq_device.h"
 #include "awq_internal.h"
 
@@ -44,6 +46,84 @@ AWQ_DEV float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// ---------------------------------------------------------------- fp8 KV rows (format: include/awq_hip.h, "fp8 KV cache")
+// A 128-value row is held 16 lanes x 8 values (lane c: dims 8c .. 8c+7), as the attention kernel reads it.
+// max over the 16 lanes of a row, same DPP moves as row16_sum; v >= 0 (|x| bit patterns of fp16: NaN > inf > every finite value,
+// so an integer max keeps a NaN that fmaxf would drop)
+AWQ_DEV int row16_max_i(int v) {
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x124, 0xF, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, false));
+    return v;
+}
+
+// codes (8 bytes) of this lane's 8 values and, in every lane of the row, the row's scale 2^k: k the smallest integer with
+// amax <= 448 * 2^k, taken from the exponent and mantissa bits of amax (448 = 1.75 * 2^8).  Zero row: scale 0, codes 0.
+// A NaN / inf anywhere in the row: scale NaN (every read of the row is then NaN), codes 0.
+AWQ_DEV u32x2 kv8_quant_row(const half8_t& h, float& scale) {
+    const u32x4 bits = __builtin_bit_cast(u32x4, h);
+    int amax = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) amax = max(amax, (int)max(bits[e] & 0x7FFFu, (bits[e] >> 16) & 0x7FFFu));
+    amax = row16_max_i(amax);
+    u32x2 w = {0u, 0u};
+    if (amax >= 0x7C00) {
+        scale = __builtin_nanf("");
+        return w;
+    }
+    if (amax == 0) {
+        scale = 0.f;
+        return w;
+    }
+    const uint32_t u = __builtin_bit_cast(uint32_t, (float)__builtin_bit_cast(half_t, (uint16_t)amax));  // fp32-normal: >= 2^-24
+    const int k = (int)(u >> 23) - 127 - 8 + ((u & 0x7FFFFF) > 0x600000 ? 1 : 0);                       // -32 .. 8
+    scale = __builtin_bit_cast(float, (uint32_t)(127 + k) << 23);
+    const float inv = __builtin_bit_cast(float, (uint32_t)(127 - k) << 23);
+    float x[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = fminf(fmaxf((float)h[e] * inv, -448.f), 448.f);  // exact scaling; the clamp is a guard
+    w.x = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0, false);
+    w.x = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], (int)w.x, true);
+    w.y = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x[4], x[5], 0, false);
+    w.y = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x[6], x[7], (int)w.y, true);
+    return w;
+}
+
+// the 8 codes of a lane as fp32 (exact; the row's scale is applied by the caller)
+AWQ_DEV void kv8_decode8(u32x2 w, float* f) {
+    auto a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, false);
+    auto b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, true);
+    auto c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, false);
+    auto d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, true);
+    f[0] = a[0], f[1] = a[1], f[2] = b[0], f[3] = b[1], f[4] = c[0], f[5] = c[1], f[6] = d[0], f[7] = d[1];
+}
+
+// The attention kernel's cache arguments: a pointer to fp16 rows, or (KV8) the codes and the scales of one cache.
+struct KV8Rows {
+    uint8_t* codes;
+    float* scales;
+};
+template <bool KV8>
+using kv_rows_t = std::conditional_t<KV8, KV8Rows, half_t* __restrict__>;
+struct KV8New {  // the new token of the fused form, quantized
+    u32x2 k, v;
+    float ks, vs;
+};
+struct KV8None {};
+
+// the fp16 row of an fp8 append before it is quantized
+AWQ_DEV half_t* kv8_rowbuf() {
+    __shared__ alignas(16) half_t buf[128];  // read back as half8_t
+    return buf;
+}
+
+template <bool KV8, class RowT>
+AWQ_DEV float kv_elem(const RowT& raw, const float* dec, int e) {
+    if constexpr (KV8) return dec[e];
+    else return (float)raw[e];
 }
 
 // ---------------------------------------------------------------- RMSNorm (+ residual add)
@@ -101,12 +181,13 @@ __global__ __launch_bounds__(256) void awq_rmsnorm_kernel(const half_t* __restri
 // writes q to q_out [B*S, Hq, D], k / v to the caches [B, Tmax, Hkv, D] at row start + s.
 // ROWS (awq_rope_kv_append_rows): every sequence b has its own start, pos_dev[b] ([B] int32 on the device, never NULL) --
 // batches of prompts of different lengths (modules/fused/decode.py); clamped to [0, Tmax - 1] like the shared one.
-template <bool ROWS = false>
-__global__ __launch_bounds__(128) void awq_rope_kv_append_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ q_out,
-                                                                half_t* __restrict__ k_cache, half_t* __restrict__ v_cache,
-                                                                const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                                                                const int* __restrict__ pos_dev, int start_pos, int S, int Hq,
-                                                                int Hkv, int D, int rot, int Tmax) {
+// KV8 (awq_rope_kv_append*_fp8, D = 128: one wave): a k / v block computes its fp16 row exactly as above into LDS, then lanes
+// (r, c) quantize it 16 lanes x 8 values (kv8_quant_row) and row 0 writes the 128 codes and the scale.
+template <bool ROWS, bool KV8, class CacheT>
+AWQ_DEV void rope_kv_append_body(const half_t* qkv, half_t* q_out, CacheT* k_cache,
+                                 CacheT* v_cache, const float* cos_t, const float* sin_t,
+                                 const int* pos_dev, int start_pos, int S, int Hq, int Hkv, int D, int rot, int Tmax,
+                                 float* k_scale, float* v_scale) {
     const int slot = blockIdx.x % (Hq + 2 * Hkv), tok = blockIdx.x / (Hq + 2 * Hkv);
     const int b = tok / S, s = tok % S;
     // A device-side position (hipGraph replay) is not seen by the host checks: clamp it to the cache so that a
@@ -117,6 +198,7 @@ __global__ __launch_bounds__(128) void awq_rope_kv_append_kernel(const half_t* _
     const half_t* src = qkv + (int64_t)tok * (Hq + 2 * Hkv) * D + (int64_t)slot * D;
     half_t* dst;
     if (slot < Hq) dst = q_out + ((int64_t)tok * Hq + slot) * D;
+    else if constexpr (KV8) dst = kv8_rowbuf();
     else if (slot < Hq + Hkv) dst = k_cache + (((int64_t)b * Tmax + pos) * Hkv + (slot - Hq)) * D;
     else dst = v_cache + (((int64_t)b * Tmax + pos) * Hkv + (slot - Hq - Hkv)) * D;
     const int half_rot = rot >> 1;
@@ -133,6 +215,39 @@ __global__ __launch_bounds__(128) void awq_rope_kv_append_kernel(const half_t* _
         dst[2 * i] = src[2 * i];
         dst[2 * i + 1] = src[2 * i + 1];
     }
+    if constexpr (KV8) {
+        if (slot >= Hq) {  // (block-uniform)
+            __syncthreads();
+            const int c = threadIdx.x & 15;
+            float sc;
+            const u32x2 w = kv8_quant_row(*reinterpret_cast<const half8_t*>(dst + 8 * c), sc);
+            const bool is_k = slot < Hq + Hkv;
+            const int64_t row = ((int64_t)b * Tmax + pos) * Hkv + (is_k ? slot - Hq : slot - Hq - Hkv);
+            if (threadIdx.x < 16) *reinterpret_cast<u32x2*>((is_k ? k_cache : v_cache) + row * 128 + 8 * c) = w;
+            if (threadIdx.x == 0) (is_k ? k_scale : v_scale)[row] = sc;
+        }
+    }
+}
+
+template <bool ROWS = false>
+__global__ __launch_bounds__(128) void awq_rope_kv_append_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ q_out,
+                                                                half_t* __restrict__ k_cache, half_t* __restrict__ v_cache,
+                                                                const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                                const int* __restrict__ pos_dev, int start_pos, int S, int Hq,
+                                                                int Hkv, int D, int rot, int Tmax) {
+    rope_kv_append_body<ROWS, false>(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos_dev, start_pos, S, Hq, Hkv, D, rot, Tmax,
+                                     nullptr, nullptr);
+}
+
+template <bool ROWS>
+__global__ __launch_bounds__(64) void awq_rope_kv_append_fp8_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ q_out,
+                                                                   uint8_t* __restrict__ k_cache, uint8_t* __restrict__ v_cache,
+                                                                   float* __restrict__ k_scale, float* __restrict__ v_scale,
+                                                                   const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                                   const int* __restrict__ pos_dev, int start_pos, int S, int Hq,
+                                                                   int Hkv, int rot, int Tmax) {
+    rope_kv_append_body<ROWS, true>(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos_dev, start_pos, S, Hq, Hkv, 128, rot, Tmax,
+                                    k_scale, v_scale);
 }
 
 // ---------------------------------------------------------------- single-query attention over the cache
@@ -157,14 +272,20 @@ __global__ __launch_bounds__(128) void awq_rope_kv_append_kernel(const half_t* _
 // ROWS (the *_rows entry points): len_dev is [B], sequence b reads its own length (FUSED: position) from len_dev[b].  The launch
 // is still sized on the host for the bucket's bound; a block deals the rows of ITS sequence to the splits, so a short sequence in
 // a long bucket leaves the last splits empty -- they write the (-inf, 0) partial the combine kernel gives weight 0.
-template <int G, bool FUSED, bool EXTRA = false, bool ROWS = false>
-__global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __restrict__ q, half_t* __restrict__ kc,
-                                                             half_t* __restrict__ vc, half_t* __restrict__ out,
+// KV8 (the *_fp8 entry points): kc / vc are KV8Rows, the caches hold e4m3 codes, one byte per value, and their `scales` one
+// fp32 scale per (sequence, row, KV head).  Same geometry: lane (r, c) loads the 8 bytes [8c, 8c+8) of its row, and the row's two
+// scales in the same round trip; the score is scale_k * sum q*code, the V weight p * scale_v.  FUSED quantizes the new token's
+// k / v (kv8_quant_row) and uses the quantized values for its own score and value, as append + plain would.
+template <int G, bool FUSED, bool EXTRA = false, bool ROWS = false, bool KV8 = false>
+__global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __restrict__ q, kv_rows_t<KV8> kc,
+                                                             kv_rows_t<KV8> vc, half_t* __restrict__ out,
                                                              float* __restrict__ part, const int* __restrict__ len_dev,
                                                              int seq_len, int Hq, int Hkv, int Tmax, float scale,
                                                              int chunk, const float* __restrict__ cos_t,
                                                              const float* __restrict__ sin_t, float softcap,
                                                              const float* __restrict__ alibi) {
+    using CacheT = std::conditional_t<KV8, uint8_t, half_t>;
+    using RowT = std::conditional_t<KV8, u32x2, half8_t>;
     static_assert(!(FUSED && EXTRA), "soft-capping / ALiBi ride on the plain form");
     constexpr int D = 128;
     __shared__ float sm[4][G][D + 2];
@@ -177,21 +298,38 @@ __global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __re
     // and never used: `live` below).  Later row sets and launches with several splits request inside the loop as before.
     constexpr int U = 4;  // row sets requested before any is consumed: 8 loads of 16 bytes in flight per lane
     const int64_t rowstride = (int64_t)Hkv * D;
-    const half_t* kb = kc + ((int64_t)b * Tmax * Hkv + hk) * D + 8 * c;
-    const half_t* vb = vc + ((int64_t)b * Tmax * Hkv + hk) * D + 8 * c;
+    const CacheT* kb;
+    const CacheT* vb;
+    const float* ksb = nullptr;  // KV8: row t's scale at ksb[t * Hkv]
+    const float* vsb = nullptr;
+    if constexpr (KV8) {
+        kb = kc.codes + ((int64_t)b * Tmax * Hkv + hk) * D + 8 * c;
+        vb = vc.codes + ((int64_t)b * Tmax * Hkv + hk) * D + 8 * c;
+        ksb = kc.scales + (int64_t)b * Tmax * Hkv + hk;
+        vsb = vc.scales + (int64_t)b * Tmax * Hkv + hk;
+    } else {
+        kb = kc + ((int64_t)b * Tmax * Hkv + hk) * D + 8 * c;
+        vb = vc + ((int64_t)b * Tmax * Hkv + hk) * D + 8 * c;
+    }
 #ifndef AWQ_ATTN_NO_EARLY
 #define AWQ_ATTN_NO_EARLY 0  // experiment builds: 1 = request every row set inside the loop (round 3's order)
 #endif
     const bool early = gridDim.x == 1 && !AWQ_ATTN_NO_EARLY;
-    half8_t kv0[U], vv0[U];
+    RowT kv0[U], vv0[U];
+    float ks0[U], vs0[U];  // KV8: the rows' scales
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int t = 4 * wave + 16 * u + r;
-        kv0[u] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+        kv0[u] = RowT{};
         vv0[u] = kv0[u];
+        ks0[u] = vs0[u] = 0.f;
         if (early && t < Tmax) {
-            kv0[u] = *reinterpret_cast<const half8_t*>(kb + (int64_t)t * rowstride);
-            vv0[u] = *reinterpret_cast<const half8_t*>(vb + (int64_t)t * rowstride);
+            kv0[u] = *reinterpret_cast<const RowT*>(kb + (int64_t)t * rowstride);
+            vv0[u] = *reinterpret_cast<const RowT*>(vb + (int64_t)t * rowstride);
+            if constexpr (KV8) {
+                ks0[u] = ksb[(int64_t)t * Hkv];
+                vs0[u] = vsb[(int64_t)t * Hkv];
+            }
         }
     }
     // device-side lengths are clamped to the cache (see awq_rope_kv_append_kernel): never a row >= Tmax
@@ -205,6 +343,7 @@ __global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __re
 
     float qf[G][8];
     half8_t k_new = {0, 0, 0, 0, 0, 0, 0, 0}, v_new = k_new;
+    std::conditional_t<KV8, KV8New, KV8None> nq{};  // KV8: the new token's codes and scales
     if constexpr (FUSED) {
         const half_t* row = q + (int64_t)b * (Hq + 2 * Hkv) * D;
         float cs[8], sn[8];
@@ -231,7 +370,19 @@ __global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __re
         }
         k_new = rotate(*reinterpret_cast<const half8_t*>(row + (int64_t)(Hq + hk) * D + 8 * c));
         v_new = *reinterpret_cast<const half8_t*>(row + (int64_t)(Hq + Hkv + hk) * D + 8 * c);
-        if (pos >= t0 && pos < t1 && wave == 0 && r == 0) {  // append: one block, 16 lanes x 16 bytes per cache
+        if constexpr (KV8) {
+            nq.k = kv8_quant_row(k_new, nq.ks);
+            nq.v = kv8_quant_row(v_new, nq.vs);
+            if (pos >= t0 && pos < t1 && wave == 0 && r == 0) {  // append: one block, 16 lanes x 8 bytes per cache + the scales
+                const int64_t row = ((int64_t)b * Tmax + pos) * Hkv + hk;
+                *reinterpret_cast<u32x2*>(kc.codes + row * D + 8 * c) = nq.k;
+                *reinterpret_cast<u32x2*>(vc.codes + row * D + 8 * c) = nq.v;
+                if (c == 0) {
+                    kc.scales[row] = nq.ks;
+                    vc.scales[row] = nq.vs;
+                }
+            }
+        } else if (pos >= t0 && pos < t1 && wave == 0 && r == 0) {  // append: one block, 16 lanes x 16 bytes per cache
             *reinterpret_cast<half8_t*>(kc + (((int64_t)b * Tmax + pos) * Hkv + hk) * D + 8 * c) = k_new;
             *reinterpret_cast<half8_t*>(vc + (((int64_t)b * Tmax + pos) * Hkv + hk) * D + 8 * c) = v_new;
         }
@@ -256,22 +407,37 @@ __global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __re
         for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
     }
     for (int tb = t0 + 4 * wave; tb < t1; tb += 16 * U) {  // wave-uniform trip count
-        half8_t kv[U], vv[U];
+        RowT kv[U], vv[U];
+        float ks[U], vs[U];
         const bool first = early && tb == 4 * wave;  // (uniform) these row sets were requested at the top of the kernel
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int t = tb + 16 * u + r;
             kv[u] = kv0[u];
             vv[u] = vv0[u];
+            ks[u] = ks0[u];
+            vs[u] = vs0[u];
             if (!first) {
-                kv[u] = half8_t{0, 0, 0, 0, 0, 0, 0, 0};
+                kv[u] = RowT{};
                 vv[u] = kv[u];
+                ks[u] = vs[u] = 0.f;
                 if (t < t1 && !(FUSED && t == pos)) {
-                    kv[u] = *reinterpret_cast<const half8_t*>(kb + (int64_t)t * rowstride);
-                    vv[u] = *reinterpret_cast<const half8_t*>(vb + (int64_t)t * rowstride);
+                    kv[u] = *reinterpret_cast<const RowT*>(kb + (int64_t)t * rowstride);
+                    vv[u] = *reinterpret_cast<const RowT*>(vb + (int64_t)t * rowstride);
+                    if constexpr (KV8) {
+                        ks[u] = ksb[(int64_t)t * Hkv];
+                        vs[u] = vsb[(int64_t)t * Hkv];
+                    }
                 }
             }
-            if (FUSED && t == pos) {  // the new token: from the qkv row, not from the cache
+            if constexpr (KV8) {
+                if (FUSED && t == pos) {  // the new token, quantized
+                    kv[u] = nq.k;
+                    vv[u] = nq.v;
+                    ks[u] = nq.ks;
+                    vs[u] = nq.vs;
+                }
+            } else if (FUSED && t == pos) {  // the new token: from the qkv row, not from the cache
                 kv[u] = k_new;
                 vv[u] = v_new;
             }
@@ -279,12 +445,18 @@ __global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __re
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const bool live = tb + 16 * u + r < t1;
+            float kd[8], vd[8];  // KV8: the codes as fp32
+            if constexpr (KV8) {
+                kv8_decode8(kv[u], kd);
+                kv8_decode8(vv[u], vd);
+            }
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 float s = 0.f;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) s += qf[g][e] * (float)kv[u][e];
+                for (int e = 0; e < 8; ++e) s += qf[g][e] * kv_elem<KV8>(kv[u], kd, e);
                 s = row16_sum(s, early);  // sum over the 16 lanes of the row
+                if constexpr (KV8) s *= ks[u];
                 if constexpr (EXTRA) {
                     if (inv_cap > 0.f) s = softcap * tanhf(s * inv_cap);
                     s += slope[g] * (float)(tb + 16 * u + r - pos);
@@ -293,8 +465,9 @@ __global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __re
                     const float mn = fmaxf(m[g], s);
                     const float corr = __expf(m[g] - mn), p = __expf(s - mn);
                     l[g] = l[g] * corr + p;
+                    const float pv = KV8 ? p * vs[u] : p;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) o[g][e] = o[g][e] * corr + p * (float)vv[u][e];
+                    for (int e = 0; e < 8; ++e) o[g][e] = o[g][e] * corr + pv * kv_elem<KV8>(vv[u], vd, e);
                     m[g] = mn;
                 }
             }
@@ -336,6 +509,15 @@ __global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __re
             const float cw = (sm[w][g][D] == -INFINITY) ? 0.f : __expf(sm[w][g][D] - mn);
             acc += sm[w][g][d] * cw;
             ls += sm[w][g][D + 1] * cw;
+        }
+        if constexpr (KV8) {
+            // a NaN scale (a row that held a NaN or an inf) makes the weights NaN, and `ls > 0` below would turn that into 0: keep it
+            // NaN, also through the combine kernel (this split then carries all the weight: NaN / inf)
+            if (ls != ls) {
+                acc = __builtin_nanf("");
+                ls = INFINITY;
+                mn = 3.402823466e38f;
+            }
         }
         const int64_t head = (int64_t)b * Hq + hk * G + g;
         if (nsplit == 1) {
@@ -380,6 +562,43 @@ __global__ __launch_bounds__(128) void awq_decode_attn_combine_kernel(const floa
     out[head * D + d] = (half_t)(denom > 0.f ? acc / denom : 0.f);
 }
 
+// ---------------------------------------------------------------- fp8 cache rows <-> fp16 (prefill workspace, update_kv, tests)
+// 16 lanes per (sequence, row, KV head), 8 values each; 256 threads = 16 rows per block.  Row i of the flat [B, n, Hkv] index is
+// cache row (b, start + t, h) of a [*, Tmax, Hkv, 128] cache.
+// dequant: out [B, n, Hkv, 128] fp16 = fp16(code * scale) for cache rows [0, n), saturated to +-65504 (a NaN scale stays NaN).
+__global__ __launch_bounds__(256) void awq_kv_dequant_fp8_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ scales,
+                                                                 half_t* __restrict__ out, int n, int Hkv, int Tmax, int64_t rows) {
+    const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int c = threadIdx.x & 15;
+    if (i >= rows) return;
+    const int64_t per = (int64_t)n * Hkv, src = (i / per) * Tmax * Hkv + i % per;
+    const u32x2 w = *reinterpret_cast<const u32x2*>(codes + src * 128 + 8 * c);
+    const float sc = scales[src];
+    float f[8];
+    kv8_decode8(w, f);
+    half8_t o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float v = f[e] * sc;
+        o[e] = (half_t)(fabsf(v) > 65504.f ? copysignf(65504.f, v) : v);
+    }
+    *reinterpret_cast<half8_t*>(out + i * 128 + 8 * c) = o;
+}
+
+// quant: x [B, S, Hkv, 128] fp16 -> codes and scales of cache rows [start, start + S)
+__global__ __launch_bounds__(256) void awq_kv_quant_fp8_kernel(const half_t* __restrict__ x, uint8_t* __restrict__ codes,
+                                                               float* __restrict__ scales, int S, int Hkv, int Tmax, int start,
+                                                               int64_t rows) {
+    const int64_t i = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int c = threadIdx.x & 15;
+    if (i >= rows) return;  // (whole 16-lane rows: the DPP max stays inside live lanes)
+    const int64_t per = (int64_t)S * Hkv, dst = (i / per) * Tmax * Hkv + (int64_t)start * Hkv + i % per;
+    float sc;
+    const u32x2 w = kv8_quant_row(*reinterpret_cast<const half8_t*>(x + i * 128 + 8 * c), sc);
+    *reinterpret_cast<u32x2*>(codes + dst * 128 + 8 * c) = w;
+    if (c == 0) scales[dst] = sc;
+}
+
 }  // namespace
 
 int awq_launch_rmsnorm(const uint16_t* x, uint16_t* residual, const uint16_t* w, uint16_t* out, int64_t M, int64_t H,
@@ -398,13 +617,23 @@ int awq_launch_rmsnorm(const uint16_t* x, uint16_t* residual, const uint16_t* w,
 
 int awq_launch_rope_kv_append(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, const float* cos_t,
                               const float* sin_t, const int32_t* pos_dev, int start_pos, int B, int S, int Hq, int Hkv, int D,
-                              int rot, int Tmax, hipStream_t st, bool rows) {
+                              int rot, int Tmax, hipStream_t st, bool rows, float* k_scale, float* v_scale) {
     if (B < 0 || S < 0 || Hq < 1 || Hkv < 1 || D < 2 || D % 2 || D > 256 || rot < 0 || rot > D || rot % 2)
         return AWQ_ERR_BAD_SHAPE;
     if (rows && !pos_dev) return AWQ_ERR_NULL;
     if (!pos_dev && (start_pos < 0 || start_pos + S > Tmax)) return AWQ_ERR_BAD_SHAPE;
+    const bool kv8 = k_scale != nullptr;
+    if (kv8 && (!v_scale)) return AWQ_ERR_NULL;
+    if (kv8 && D != 128) return AWQ_ERR_UNSUPPORTED;
     if (B * S == 0) return AWQ_OK;
     const unsigned blocks = (unsigned)((int64_t)B * S * (Hq + 2 * Hkv));
+    if (kv8) {
+        hipLaunchKernelGGL(rows ? awq_rope_kv_append_fp8_kernel<true> : awq_rope_kv_append_fp8_kernel<false>, dim3(blocks), dim3(64), 0,
+                           st, reinterpret_cast<const half_t*>(qkv), reinterpret_cast<half_t*>(q_out),
+                           reinterpret_cast<uint8_t*>(k_cache), reinterpret_cast<uint8_t*>(v_cache), k_scale, v_scale, cos_t, sin_t,
+                           pos_dev, start_pos, S, Hq, Hkv, rot, Tmax);
+        return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
+    }
     hipLaunchKernelGGL(rows ? awq_rope_kv_append_kernel<true> : awq_rope_kv_append_kernel<false>, dim3(blocks), dim3(D / 2), 0, st,
                        reinterpret_cast<const half_t*>(qkv), reinterpret_cast<half_t*>(q_out), reinterpret_cast<half_t*>(k_cache),
                        reinterpret_cast<half_t*>(v_cache), cos_t, sin_t, pos_dev, start_pos, S, Hq, Hkv, D, rot, Tmax);
@@ -415,10 +644,18 @@ size_t awq_decode_attention_workspace_bytes_impl(int B, int Hq, int max_splits) 
     return (size_t)B * Hq * max_splits * (128 + 2) * sizeof(float);
 }
 
+// ksc != nullptr: the fp8 kernel (codes in kc / vc, scales in ksc / vsc)
 template <int G, bool FUSED, bool EXTRA = false, bool ROWS = false>
-static void launch_attn(dim3 grid, hipStream_t st, const uint16_t* q, uint16_t* kc, uint16_t* vc, uint16_t* out, float* part,
-                        const int32_t* len_dev, int seq_len, int Hq, int Hkv, int Tmax, float scale, int chunk,
-                        const float* cos_t, const float* sin_t, float softcap = 0.f, const float* alibi = nullptr) {
+static void launch_attn(dim3 grid, hipStream_t st, float* ksc, float* vsc, const uint16_t* q, uint16_t* kc, uint16_t* vc,
+                        uint16_t* out, float* part, const int32_t* len_dev, int seq_len, int Hq, int Hkv, int Tmax, float scale,
+                        int chunk, const float* cos_t, const float* sin_t, float softcap = 0.f, const float* alibi = nullptr) {
+    if (ksc) {
+        hipLaunchKernelGGL((awq_decode_attn_kernel<G, FUSED, EXTRA, ROWS, true>), grid, dim3(256), 0, st, reinterpret_cast<const half_t*>(q),
+                           KV8Rows{reinterpret_cast<uint8_t*>(kc), ksc}, KV8Rows{reinterpret_cast<uint8_t*>(vc), vsc},
+                           reinterpret_cast<half_t*>(out), part, len_dev, seq_len, Hq, Hkv, Tmax, scale, chunk, cos_t, sin_t, softcap,
+                           alibi);
+        return;
+    }
     hipLaunchKernelGGL((awq_decode_attn_kernel<G, FUSED, EXTRA, ROWS>), grid, dim3(256), 0, st, reinterpret_cast<const half_t*>(q),
                        reinterpret_cast<half_t*>(kc), reinterpret_cast<half_t*>(vc), reinterpret_cast<half_t*>(out), part,
                        len_dev, seq_len, Hq, Hkv, Tmax, scale, chunk, cos_t, sin_t, softcap, alibi);
@@ -429,8 +666,10 @@ static void launch_attn(dim3 grid, hipStream_t st, const uint16_t* q, uint16_t* 
 int awq_launch_decode_attention(const uint16_t* q, uint16_t* k_cache, uint16_t* v_cache, uint16_t* out,
                                 const int32_t* len_dev, int seq_len, int max_len, int B, int Hq, int Hkv, int D, int Tmax,
                                 float scale, void* workspace, size_t workspace_bytes, const float* cos_t,
-                                const float* sin_t, hipStream_t st, float softcap, const float* alibi, bool rows) {
+                                const float* sin_t, hipStream_t st, float softcap, const float* alibi, bool rows, float* k_scale,
+                                float* v_scale) {
     if (rows && !len_dev) return AWQ_ERR_NULL;
+    if ((k_scale == nullptr) != (v_scale == nullptr)) return AWQ_ERR_NULL;
     if (D != 128) return AWQ_ERR_UNSUPPORTED;
     const bool extra = softcap > 0.f || alibi != nullptr;
     if (extra && cos_t) return AWQ_ERR_UNSUPPORTED;  // ALiBi models do not rotate; soft-capping takes the two-launch form
@@ -475,17 +714,17 @@ int awq_launch_decode_attention(const uint16_t* q, uint16_t* k_cache, uint16_t* 
 #define AWQ_ATTN_CASE(GG)                                                                                                  \
     case GG:                                                                                                               \
         if (rows) {                                                                                                        \
-            if (extra) launch_attn<GG, false, true, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, \
+            if (extra) launch_attn<GG, false, true, true>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, \
                                                           Tmax, scale, chunk, nullptr, nullptr, softcap, alibi);           \
-            else if (fused) launch_attn<GG, true, false, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, \
+            else if (fused) launch_attn<GG, true, false, true>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, \
                                                                Hkv, Tmax, scale, chunk, cos_t, sin_t);                     \
-            else launch_attn<GG, false, false, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, \
+            else launch_attn<GG, false, false, true>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, \
                                                      scale, chunk, nullptr, nullptr);                                      \
-        } else if (extra) launch_attn<GG, false, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, \
+        } else if (extra) launch_attn<GG, false, true>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, \
                                                 scale, chunk, nullptr, nullptr, softcap, alibi);                            \
-        else if (fused) launch_attn<GG, true>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, scale, \
+        else if (fused) launch_attn<GG, true>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, scale, \
                                          chunk, cos_t, sin_t);                                                             \
-        else launch_attn<GG, false>(grid, st, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, scale,      \
+        else launch_attn<GG, false>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, scale,      \
                                     chunk, nullptr, nullptr);                                                              \
         break;
     switch (G) {
@@ -503,4 +742,24 @@ int awq_launch_decode_attention(const uint16_t* q, uint16_t* k_cache, uint16_t* 
         if (hipGetLastError() != hipSuccess) return AWQ_ERR_LAUNCH;
     }
     return AWQ_OK;
+}
+
+int awq_launch_kv_quant_fp8(const uint16_t* x, uint8_t* codes, float* scales, int B, int S, int Hkv, int Tmax, int start,
+                            hipStream_t st) {
+    if (B < 0 || S < 0 || Hkv < 1 || start < 0 || start + S > Tmax) return AWQ_ERR_BAD_SHAPE;
+    const int64_t rows = (int64_t)B * S * Hkv;
+    if (rows == 0) return AWQ_OK;
+    hipLaunchKernelGGL(awq_kv_quant_fp8_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st,
+                       reinterpret_cast<const half_t*>(x), codes, scales, S, Hkv, Tmax, start, rows);
+    return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
+}
+
+int awq_launch_kv_dequant_fp8(const uint8_t* codes, const float* scales, uint16_t* out, int B, int n, int Hkv, int Tmax,
+                              hipStream_t st) {
+    if (B < 0 || n < 0 || Hkv < 1 || n > Tmax) return AWQ_ERR_BAD_SHAPE;
+    const int64_t rows = (int64_t)B * n * Hkv;
+    if (rows == 0) return AWQ_OK;
+    hipLaunchKernelGGL(awq_kv_dequant_fp8_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, codes, scales,
+                       reinterpret_cast<half_t*>(out), n, Hkv, Tmax, rows);
+    return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }

@@ -18,13 +18,14 @@ class FusedCausalLM(nn.Module):
     """`logits = lm_head(fused_model(input_ids).last_hidden_state)`: what `LlamaForCausalLM.forward`
     does with the fused model swapped in, without depending on transformers' internals."""
 
-    def __init__(self, model, lm_head, checkpoint_layout=None, decode_layout=None):
+    def __init__(self, model, lm_head, checkpoint_layout=None, decode_layout=None, kv_cache_dtype="fp16"):
         super().__init__()
         self.model = model
         self.lm_head = lm_head
         # declared: the layout the checkpoint came in and the one its Linears were repacked to for decoding (fuse_llama)
         self.checkpoint_layout = checkpoint_layout
         self.decode_layout = decode_layout
+        self.kv_cache_dtype = kv_cache_dtype  # "fp16" or "fp8" (modules/fused/cache.py)
 
     @torch.inference_mode()
     def forward(self, input_ids):
@@ -42,7 +43,12 @@ def _layout_of(model):
     return {WQLinear_GEMM: "gemm", WQLinear_GEMV: "gemv", WQLinear_GEMVFast: "gemv_fast"}[kinds.pop()]
 
 
-def fuse_llama(hf_model, max_seq_len=2048, decode_layout="auto"):
+def _check_kv_cache_dtype(name, kv_cache_dtype):
+    if kv_cache_dtype not in ("fp16", "fp8"):
+        raise ValueError(f"{name}: kv_cache_dtype must be 'fp16' or 'fp8', got {kv_cache_dtype!r}")
+
+
+def fuse_llama(hf_model, max_seq_len=2048, decode_layout="auto", kv_cache_dtype="fp16"):
     """decode_layout:
       "auto" (default since round 4)  a checkpoint in the DEFAULT format (`AwqConfig.version == "gemm"`,
               awq/models/_config.py:8-27) is repacked -- same integers, bit-exact (utils/convert.py, pinned against
@@ -55,7 +61,10 @@ def fuse_llama(hf_model, max_seq_len=2048, decode_layout="auto"):
               packed words (csrc/repack.hip, freed after the call) under the fused MFMA GEMM -- no second resident copy;
       "gemv"  repack whatever the checkpoint's layout is;
       None    keep the checkpoint's layout (the reference's ExLlama repack at load time is the same kind of declared option:
-              awq/modules/linear/exllama.py:66-79)."""
+              awq/modules/linear/exllama.py:66-79).
+    kv_cache_dtype: "fp16" (default) or "fp8" -- e4m3 codes + one fp32 scale per row, about half the cache bytes
+              (modules/fused/cache.py); declared on the result as `.kv_cache_dtype`."""
+    _check_kv_cache_dtype("fuse_llama", kv_cache_dtype)
     cfg = hf_model.config
     src = _layout_of(hf_model.model)
     target = None
@@ -85,13 +94,14 @@ def fuse_llama(hf_model, max_seq_len=2048, decode_layout="auto"):
         blocks.append(LlamaLikeBlock(hidden_size=cfg.hidden_size, n_heads=cfg.num_attention_heads,
                                      n_kv_heads=cfg.num_key_value_heads, qkv_layer=qkv, o_proj=att.o_proj, mlp=mlp,
                                      norm_1=norm_1, norm_2=norm_2, dev=dev, max_seq_len=max_seq_len,
-                                     rope_theta=rope_theta, head_dim=getattr(cfg, "head_dim", None)))
+                                     rope_theta=rope_theta, head_dim=getattr(cfg, "head_dim", None),
+                                     kv_cache_dtype=kv_cache_dtype))
     fused = LlamaLikeModel(cfg.vocab_size, blocks, hf_model.model.embed_tokens,
                            FasterTransformerRMSNorm(hf_model.model.norm.weight, hf_model.model.norm.variance_epsilon))
-    return FusedCausalLM(fused, hf_model.lm_head, checkpoint_layout=src, decode_layout=target or src)
+    return FusedCausalLM(fused, hf_model.lm_head, checkpoint_layout=src, decode_layout=target or src, kv_cache_dtype=kv_cache_dtype)
 
 
-def fuse_mixtral(hf_model, max_seq_len=2048, decode_layout="auto"):
+def fuse_mixtral(hf_model, max_seq_len=2048, decode_layout="auto", kv_cache_dtype="fp16"):
     """`MixtralFuser.fuse_transformer` (awq/models/mixtral.py:97-187) for a Mixtral-style model in the per-expert form AWQ
     checkpoints are written in (`model.layers[i].block_sparse_moe.{gate, top_k, experts[e].{w1, w2, w3}}`): per layer fuse
     q|k|v, wrap the norms, and -- when the experts are WQLinear_GEMM -- concatenate each expert's w1|w3 on N, stack the experts
@@ -100,7 +110,9 @@ def fuse_mixtral(hf_model, max_seq_len=2048, decode_layout="auto"):
     `[E, K, N/8]` tensors of the reference: prefill-sized token counts and more than `moe.ROWS_MAX_PAIRS` pairs read those);
     with a decode layout they also get GEMV-layout TWINS (`moe.build_decode_twins`: a second resident copy of the experts, w1|w3
     with its gate / up rows interleaved), which decode-sized steps run through the row-streaming kernel -- Mixtral shape, bs = 4:
-    114 us per block against 132 us on the GEMM-layout stacks.  decode_layout=None: no repack, no twins."""
+    114 us per block against 132 us on the GEMM-layout stacks.  decode_layout=None: no repack, no twins.
+    kv_cache_dtype as in `fuse_llama`."""
+    _check_kv_cache_dtype("fuse_mixtral", kv_cache_dtype)
     cfg = hf_model.config
     src = _layout_of(hf_model.model)
     target = src
@@ -136,7 +148,7 @@ def fuse_mixtral(hf_model, max_seq_len=2048, decode_layout="auto"):
             rope_theta = (getattr(cfg, "rope_parameters", None) or {}).get("rope_theta", 10000.0)
         blocks.append(MixtralBlock(hidden_size=cfg.hidden_size, n_heads=cfg.num_attention_heads, n_kv_heads=cfg.num_key_value_heads,
                                    qkv_layer=qkv, o_proj=att.o_proj, moe=moe, norm_1=norm_1, norm_2=norm_2, dev=dev,
-                                   max_seq_len=max_seq_len, rope_theta=rope_theta))
+                                   max_seq_len=max_seq_len, rope_theta=rope_theta, kv_cache_dtype=kv_cache_dtype))
     fused = MixtralModel(cfg.vocab_size, blocks, hf_model.model.embed_tokens,
                          FasterTransformerRMSNorm(hf_model.model.norm.weight, hf_model.model.norm.variance_epsilon))
-    return FusedCausalLM(fused, hf_model.lm_head, checkpoint_layout=src, decode_layout=target)
+    return FusedCausalLM(fused, hf_model.lm_head, checkpoint_layout=src, decode_layout=target, kv_cache_dtype=kv_cache_dtype)

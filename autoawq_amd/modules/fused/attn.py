@@ -19,7 +19,12 @@ MI355X-first differences:
     back into the q | k | v head order the kernels read; ALiBi models skip the rotation (rotary width 0 in the append kernel)
     and pass their slopes, `attn_logit_softcapping` its cap, to `awq_decode_attention_ex` -- what the reference hands
     flash_attn_with_kvcache as `alibi_slopes=` / `softcap=` (attn.py:286-302).  Prefill with either modifier computes the
-    scores in torch (fp32), where the reference calls flash_attn_func with the same arguments (attn.py:277-285)."""
+    scores in torch (fp32), where the reference calls flash_attn_func with the same arguments (attn.py:277-285).
+  * `kv_cache_dtype="fp8"` (opt-in; default "fp16"): the cache holds e4m3 codes + one fp32 scale per row (WindowedCache, format in
+    include/awq_hip.h); appends and decode attention run the *_fp8 kernels.  Prefill appends in fp8, dequantizes rows
+    [0, start_pos + S) into an fp16 workspace and runs the unchanged prefill attention on it, so a prompt attends to the same
+    quantized values its decode steps will read.  Only the native head shapes take it (head_dim 128, 1 / 2 / 4 / 8 query heads per
+    KV head): other shapes slice the cache in torch and are refused at construction."""
 import math
 import os
 
@@ -81,7 +86,7 @@ class QuantAttentionFused(nn.Module):
 
     def __init__(self, hidden_size, n_heads, n_kv_heads, qkv_layer, o_proj, dev, max_seq_len=2048, use_alibi=False,
                  attention_shapes=None, rope_theta=10000, partial_rotary_factor=1.0, head_dim=None,
-                 attn_logit_softcapping=0.0, q_norm=None, k_norm=None, **kwargs):
+                 attn_logit_softcapping=0.0, q_norm=None, k_norm=None, kv_cache_dtype="fp16", **kwargs):
         super().__init__()
         from ...utils.fused_utils import get_attention_shapes
 
@@ -98,13 +103,21 @@ class QuantAttentionFused(nn.Module):
         self.attn_logit_softcapping = float(attn_logit_softcapping or 0.0)
         self._custom_shapes = attention_shapes is not None
         self.attention_shapes = get_attention_shapes(attention_shapes, n_heads, n_kv_heads, self.head_dim)
+        if kv_cache_dtype not in ("fp16", "fp8"):
+            raise ValueError(f"QuantAttentionFused: kv_cache_dtype must be 'fp16' or 'fp8', got {kv_cache_dtype!r}")
+        if kv_cache_dtype == "fp8" and not (self.head_dim == 128 and n_heads % self.n_kv_heads == 0
+                                            and self.n_kv_groups in (1, 2, 4, 8)):
+            raise ValueError(f"QuantAttentionFused: kv_cache_dtype='fp8' needs head_dim 128 and 1, 2, 4 or 8 query heads per KV head "
+                             f"(got head_dim {self.head_dim}, {n_heads} / {self.n_kv_heads} heads)")
+        self.kv_cache_dtype = kv_cache_dtype
         self.cache_batch_size = int(os.getenv("AWQ_BATCH_SIZE", "1"))
         if kwargs.get("max_length") is not None:
             max_seq_len = kwargs["max_length"]
         self.max_seq_len = max_seq_len
         self.is_hf_transformers = False
         self.rope_theta = rope_theta
-        self.cache = WindowedCache(self.cache_batch_size, n_heads, self.n_kv_heads, self.head_dim, max_seq_len, dev)
+        self.cache = WindowedCache(self.cache_batch_size, n_heads, self.n_kv_heads, self.head_dim, max_seq_len, dev,
+                                   dtype=kv_cache_dtype)
         self.partial_rotary_factor = partial_rotary_factor
         if self.use_alibi:  # no rotation (attn.py:189-194,254): the append kernel runs with rotary width 0
             self.alibi = ALiBi(n_heads, max_seq_len, dev)
@@ -202,7 +215,8 @@ class QuantAttentionFused(nn.Module):
                                             self.n_heads, self.n_kv_heads,
                                             pos_dev=self._pos_dev if device_pos and not rows else None,
                                             max_len=self._len_bound() if device_pos else None,
-                                            pos_rows=self._pos_dev if rows else None)
+                                            pos_rows=self._pos_dev if rows else None, k_scale=self.cache.k_scale,
+                                            v_scale=self.cache.v_scale)
             attention_weight = out.reshape(bsz, 1, -1)
             attn_output = self.o_proj(attention_weight) if apply_o_proj else attention_weight
             self.start_pos += 1
@@ -210,18 +224,23 @@ class QuantAttentionFused(nn.Module):
         xq = ops.rope_kv_append(xqkv, self.cache.k, self.cache.v, self.rope.cos, self.rope.sin, self.start_pos,
                                 self.n_heads, self.n_kv_heads, self.head_dim, self.rotary_dim,
                                 pos_dev=self._pos_dev if device_pos and not rows else None,
-                                pos_rows=self._pos_dev if rows else None)
+                                pos_rows=self._pos_dev if rows else None, k_scale=self.cache.k_scale, v_scale=self.cache.v_scale)
+        k_rows, v_rows = self.cache.k, self.cache.v  # what prefill attends over
+        if seqlen > 1 and self.kv_cache_dtype == "fp8":  # the appended rows, dequantized: [B, start_pos + S, Hkv, 128] fp16
+            end = self.start_pos + seqlen
+            k_rows = ops.kv_dequant_fp8(self.cache.k, self.cache.k_scale, end, bsz)
+            v_rows = ops.kv_dequant_fp8(self.cache.v, self.cache.v_scale, end, bsz)
         if seqlen > 1 and self.head_dim == 128 and self.n_heads % self.n_kv_heads == 0 and self.PREFILL_KERNEL:
             # prefill: the hand-written flash-style kernel (csrc/prefill_attn.hip; the reference's flash_attn_func call, attn.py:269-277),
             # chunked prefill, GQA, ALiBi and the soft cap included -- no mask tensor, no repeat_interleave copy of the cache
-            out = ops.prefill_attention(xq, self.cache.k, self.cache.v, self.start_pos, softcap=self.attn_logit_softcapping,
+            out = ops.prefill_attention(xq, k_rows, v_rows, self.start_pos, softcap=self.attn_logit_softcapping,
                                         alibi_slopes=self.alibi.slopes if self.alibi is not None else None)
             output = out.reshape(bsz, seqlen, -1)
         elif seqlen > 1:  # other head sizes: the vendor's attention (fp32 matmul softmax when the scores carry a bias or a cap)
             end = self.start_pos + seqlen
             q = xq.transpose(1, 2)                                  # [B, Hq, S, D]
-            k = self.cache.k[:bsz, :end].transpose(1, 2)            # [B, Hkv, T, D]
-            v = self.cache.v[:bsz, :end].transpose(1, 2)
+            k = k_rows[:bsz, :end].transpose(1, 2)                  # [B, Hkv, T, D]
+            v = v_rows[:bsz, :end].transpose(1, 2)
             if self.n_kv_groups > 1:
                 k = k.repeat_interleave(self.n_kv_groups, dim=1)
                 v = v.repeat_interleave(self.n_kv_groups, dim=1)
@@ -252,7 +271,8 @@ class QuantAttentionFused(nn.Module):
                                            len_dev=self._len_dev if device_pos and not rows else None, max_len=self._len_bound(),
                                            softcap=self.attn_logit_softcapping,
                                            alibi_slopes=self.alibi.slopes if self.alibi is not None else None,
-                                           len_rows=self._len_dev if rows else None)
+                                           len_rows=self._len_dev if rows else None, k_scale=self.cache.k_scale,
+                                           v_scale=self.cache.v_scale)
                 output = out.reshape(bsz, 1, -1)
         attention_weight = output
         attn_output = self.o_proj(attention_weight) if apply_o_proj else attention_weight

@@ -17,14 +17,16 @@ class MixtralBlock(nn.Module):
     is hipGraph-capturable).  As in LlamaLikeBlock the first residual add rides on norm_2 (`FasterTransformerRMSNorm(x,
     residual=...)`: one launch, the sum lands in o_proj's own output buffer)."""
 
-    def __init__(self, hidden_size, n_heads, n_kv_heads, qkv_layer, o_proj, moe, norm_1, norm_2, dev, max_seq_len, rope_theta):
+    def __init__(self, hidden_size, n_heads, n_kv_heads, qkv_layer, o_proj, moe, norm_1, norm_2, dev, max_seq_len, rope_theta,
+                 kv_cache_dtype="fp16"):
         super().__init__()
         self.n_heads = n_heads
         self.n_kv_heads = n_kv_heads
         self.hidden_size = hidden_size
         self.norm_1 = norm_1.to(dev)
         self.attn = QuantAttentionFused(self.hidden_size, self.n_heads, self.n_kv_heads, qkv_layer, o_proj, dev=dev,
-                                        max_seq_len=max_seq_len, use_alibi=False, rope_theta=rope_theta).to(dev)
+                                        max_seq_len=max_seq_len, use_alibi=False, rope_theta=rope_theta,
+                                        kv_cache_dtype=kv_cache_dtype).to(dev)
         self.norm_2 = norm_2.to(dev)
         self.moe = moe
         self.device = dev
@@ -44,7 +46,7 @@ class MixtralBlock(nn.Module):
 
 class LlamaLikeBlock(nn.Module):
     def __init__(self, hidden_size, n_heads, n_kv_heads, qkv_layer, o_proj, mlp, norm_1, norm_2, dev, max_seq_len,
-                 rope_theta=10000, partial_rotary_factor=1.0, use_alibi=False, head_dim=None):
+                 rope_theta=10000, partial_rotary_factor=1.0, use_alibi=False, head_dim=None, kv_cache_dtype="fp16"):
         super().__init__()
         self.n_heads = n_heads
         self.n_kv_heads = n_kv_heads
@@ -53,7 +55,8 @@ class LlamaLikeBlock(nn.Module):
         self.norm_1 = norm_1.to(dev)
         self.attn = QuantAttentionFused(self.hidden_size, self.n_heads, self.n_kv_heads, qkv_layer, o_proj, dev=dev,
                                         max_seq_len=max_seq_len, use_alibi=use_alibi, rope_theta=rope_theta,
-                                        partial_rotary_factor=partial_rotary_factor, head_dim=head_dim).to(dev)
+                                        partial_rotary_factor=partial_rotary_factor, head_dim=head_dim,
+                                        kv_cache_dtype=kv_cache_dtype).to(dev)
         self.norm_2 = norm_2.to(dev)
         self.mlp = mlp.to(dev)
         self.device = dev

@@ -693,17 +693,53 @@ def _check_rows(name, what, rows, shared, B, device):
         raise _lib.AwqHipError(f"{name}: {what}_rows must be a contiguous [{B}] tensor, got {tuple(rows.shape)}")
 
 
+def _kv8(name, k_cache, v_cache, k_scale, v_scale):
+    """True for an fp8 cache (uint8 codes [B, Tmax, Hkv, 128] + fp32 scales [B, Tmax, Hkv], include/awq_hip.h), False for
+    fp16; a uint8 cache without its scales, or scales next to an fp16 cache, is an error."""
+    codes = k_cache.dtype == torch.uint8 or v_cache.dtype == torch.uint8
+    scales = k_scale is not None or v_scale is not None
+    if not codes and not scales:
+        return False
+    if not codes:
+        raise _lib.AwqHipError(f"{name}: k_scale / v_scale belong to an fp8 (uint8) cache, got {k_cache.dtype}")
+    if k_scale is None or v_scale is None:
+        raise _lib.AwqHipError(f"{name}: an fp8 (uint8) cache needs both k_scale and v_scale")
+    if k_cache.dtype != v_cache.dtype:
+        raise _lib.AwqHipError(f"{name}: k and v caches differ in dtype ({k_cache.dtype}, {v_cache.dtype})")
+    for sc, c in ((k_scale, k_cache), (v_scale, v_cache)):
+        if sc.dtype != torch.float32 or not sc.is_contiguous() or tuple(sc.shape) != tuple(c.shape[:3]):
+            raise _lib.AwqHipError(f"{name}: scales must be contiguous fp32 {tuple(c.shape[:3])}, got {sc.dtype} {tuple(sc.shape)}")
+        if sc.device != c.device:
+            raise _lib.AwqHipError(f"{name}: scales and cache on different devices")
+    return True
+
+
 def rope_kv_append(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n_kv_heads, head_dim, rotary_dim, pos_dev=None,
-                   pos_rows=None):
+                   pos_rows=None, k_scale=None, v_scale=None):
     """qkv [B, S, (Hq + 2 Hkv) * D] fp16 -> rotated q [B, S, Hq, D]; rotated k and v are written into
     the caches [B, Tmax, Hkv, D] at rows start_pos .. start_pos + S - 1 (awq_rope_kv_append).  pos_rows (int32 [B] on the
-    device; start_pos is then ignored): sequence b starts at pos_rows[b] (awq_rope_kv_append_rows)."""
-    _require_gpu(qkv, k_cache, v_cache, cos, sin, pos_dev, pos_rows)
+    device; start_pos is then ignored): sequence b starts at pos_rows[b] (awq_rope_kv_append_rows).  k_scale / v_scale
+    ([B, Tmax, Hkv] fp32) with uint8 caches: the fp8 cache -- rows are stored as e4m3 codes + scales (awq_rope_kv_append*_fp8)."""
+    kv8 = _kv8("rope_kv_append", k_cache, v_cache, k_scale, v_scale)
+    _require_gpu(qkv, k_cache, v_cache, cos, sin, pos_dev, pos_rows, k_scale, v_scale)
     B, S = qkv.shape[0], qkv.shape[1]
     qkv = qkv.contiguous()
     q = torch.empty((B, S, n_heads, head_dim), dtype=torch.float16, device=qkv.device)
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()) or k_cache.shape[0] < B:
         raise _lib.AwqHipError("rope_kv_append: caches must be contiguous [>=B, Tmax, Hkv, D]")
+    if kv8:
+        L = _lib.lib()
+        with torch.cuda.device(qkv.device):
+            if pos_rows is not None:
+                _check_rows("rope_kv_append", "pos", pos_rows, pos_dev, B, qkv.device)
+                _lib.check(L.awq_rope_kv_append_rows_fp8(_ptr(qkv), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
+                                                         _ptr(cos), _ptr(sin), _ptr(pos_rows), B, S, n_heads, n_kv_heads, head_dim,
+                                                         rotary_dim, k_cache.shape[1], _stream()), "awq_rope_kv_append_rows_fp8")
+            else:
+                _lib.check(L.awq_rope_kv_append_fp8(_ptr(qkv), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
+                                                    _ptr(cos), _ptr(sin), _ptr(pos_dev), int(start_pos), B, S, n_heads, n_kv_heads,
+                                                    head_dim, rotary_dim, k_cache.shape[1], _stream()), "awq_rope_kv_append_fp8")
+        return q
     if pos_rows is not None:
         _check_rows("rope_kv_append", "pos", pos_rows, pos_dev, B, qkv.device)
         with torch.cuda.device(qkv.device):
@@ -747,12 +783,14 @@ _attn_workspaces = {}
 
 
 def decode_attention(q, k_cache, v_cache, seq_len, scale=None, len_dev=None, max_len=None, softcap=0.0, alibi_slopes=None,
-                     len_rows=None):
+                     len_rows=None, k_scale=None, v_scale=None):
     """q [B, Hq, 128] fp16, caches [B, Tmax, Hkv, 128] -> [B, Hq, 128]: attention of ONE query token per
     sequence over cache rows [0, seq_len) (awq_decode_attention; with logit soft-capping / ALiBi slopes [Hq] fp32:
     awq_decode_attention_ex).  len_rows (int32 [B] on the device; seq_len is then ignored): sequence b attends over rows
-    [0, len_rows[b]), the launch sized for max_len (default: the cache window) -- awq_decode_attention_rows."""
-    _require_gpu(q, k_cache, v_cache, len_dev, alibi_slopes, len_rows)
+    [0, len_rows[b]), the launch sized for max_len (default: the cache window) -- awq_decode_attention_rows.  k_scale /
+    v_scale with uint8 caches: the fp8 cache (the *_fp8 entry points)."""
+    kv8 = _kv8("decode_attention", k_cache, v_cache, k_scale, v_scale)
+    _require_gpu(q, k_cache, v_cache, len_dev, alibi_slopes, len_rows, k_scale, v_scale)
     B, Hq, D = q.shape
     Hkv, Tmax = k_cache.shape[2], k_cache.shape[1]
     q = q.contiguous()
@@ -772,6 +810,20 @@ def decode_attention(q, k_cache, v_cache, seq_len, scale=None, len_dev=None, max
         alibi_slopes = alibi_slopes.to(torch.float32).contiguous()
         if alibi_slopes.numel() != Hq:
             raise _lib.AwqHipError("decode_attention: alibi_slopes must hold one slope per query head")
+    if kv8:
+        with torch.cuda.device(q.device):
+            if len_rows is not None:
+                _check_rows("decode_attention", "len", len_rows, len_dev, B, q.device)
+                _lib.check(L.awq_decode_attention_rows_fp8(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(out),
+                                                           _ptr(len_rows), int(max_len if max_len is not None else Tmax), B, Hq, Hkv, D,
+                                                           Tmax, float(scale), float(softcap), _ptr(alibi_slopes), _ptr(ws), ws.numel(),
+                                                           _stream()), "awq_decode_attention_rows_fp8")
+            else:
+                _lib.check(L.awq_decode_attention_ex_fp8(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(out),
+                                                         _ptr(len_dev), int(seq_len), int(max_len if max_len is not None else seq_len),
+                                                         B, Hq, Hkv, D, Tmax, float(scale), float(softcap), _ptr(alibi_slopes),
+                                                         _ptr(ws), ws.numel(), _stream()), "awq_decode_attention_ex_fp8")
+        return out
     if len_rows is not None:
         _check_rows("decode_attention", "len", len_rows, len_dev, B, q.device)
         with torch.cuda.device(q.device):
@@ -794,13 +846,15 @@ def decode_attention(q, k_cache, v_cache, seq_len, scale=None, len_dev=None, max
 
 
 def decode_attention_rope(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n_kv_heads, pos_dev=None, max_len=None,
-                          scale=None, pos_rows=None):
+                          scale=None, pos_rows=None, k_scale=None, v_scale=None):
     """One launch for a decode step: qkv [B, 1, (Hq + 2 Hkv) * 128] (or [B, ...]) -> attention output
     [B, Hq, 128]; rotates q / k, appends k / v at row start_pos and attends over rows [0, start_pos]
     (awq_decode_attention_rope; bit-identical to rope_kv_append + decode_attention).  pos_rows (int32 [B] on the device;
     start_pos is then ignored): sequence b at position pos_rows[b], the launch sized for max_len (default: the cache window)
-    -- awq_decode_attention_rope_rows."""
-    _require_gpu(qkv, k_cache, v_cache, cos, sin, pos_dev, pos_rows)
+    -- awq_decode_attention_rope_rows.  k_scale / v_scale with uint8 caches: the fp8 cache -- the new token is quantized,
+    appended as codes + scales and attended to in its quantized form (the *_fp8 entry points)."""
+    kv8 = _kv8("decode_attention_rope", k_cache, v_cache, k_scale, v_scale)
+    _require_gpu(qkv, k_cache, v_cache, cos, sin, pos_dev, pos_rows, k_scale, v_scale)
     B = qkv.shape[0]
     D = k_cache.shape[3]
     qkv = qkv.contiguous()
@@ -816,6 +870,22 @@ def decode_attention_rope(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n
         _attn_workspaces[key] = ws
     if scale is None:
         scale = D ** -0.5
+    if kv8:
+        with torch.cuda.device(qkv.device):
+            if pos_rows is not None:
+                _check_rows("decode_attention_rope", "pos", pos_rows, pos_dev, B, qkv.device)
+                _lib.check(L.awq_decode_attention_rope_rows_fp8(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
+                                                                _ptr(cos), _ptr(sin), _ptr(out), _ptr(pos_rows),
+                                                                int(max_len if max_len is not None else k_cache.shape[1]), B, n_heads,
+                                                                n_kv_heads, D, k_cache.shape[1], float(scale), _ptr(ws), ws.numel(),
+                                                                _stream()), "awq_decode_attention_rope_rows_fp8")
+            else:
+                _lib.check(L.awq_decode_attention_rope_fp8(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
+                                                           _ptr(cos), _ptr(sin), _ptr(out), _ptr(pos_dev), int(start_pos),
+                                                           int(max_len if max_len is not None else start_pos + 1), B, n_heads,
+                                                           n_kv_heads, D, k_cache.shape[1], float(scale), _ptr(ws), ws.numel(),
+                                                           _stream()), "awq_decode_attention_rope_fp8")
+        return out
     if pos_rows is not None:
         _check_rows("decode_attention_rope", "pos", pos_rows, pos_dev, B, qkv.device)
         with torch.cuda.device(qkv.device):
@@ -830,6 +900,39 @@ def decode_attention_rope(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n
                                                int(max_len if max_len is not None else start_pos + 1), B, n_heads,
                                                n_kv_heads, D, k_cache.shape[1], float(scale), _ptr(ws), ws.numel(),
                                                _stream()), "awq_decode_attention_rope")
+    return out
+
+
+def kv_quant_fp8(x, cache, scales, start_pos=0):
+    """x [B, S, Hkv, 128] fp16 -> e4m3 codes and scales of rows [start_pos, start_pos + S) of the fp8 cache `cache` [>= B, Tmax,
+    Hkv, 128] uint8 / `scales` [>= B, Tmax, Hkv] fp32, in place (awq_kv_quant_fp8; format: include/awq_hip.h)."""
+    _require_gpu(x, cache, scales)
+    if x.dtype != torch.float16 or cache.dtype != torch.uint8 or scales.dtype != torch.float32:
+        raise _lib.AwqHipError("kv_quant_fp8 expects fp16 rows, a uint8 cache and fp32 scales")
+    if x.dim() != 4 or cache.dim() != 4 or tuple(scales.shape) != tuple(cache.shape[:3]) or x.shape[0] > cache.shape[0] \
+            or tuple(x.shape[2:]) != tuple(cache.shape[2:]) or not (cache.is_contiguous() and scales.is_contiguous()):
+        raise _lib.AwqHipError(f"kv_quant_fp8: shapes {tuple(x.shape)}, {tuple(cache.shape)}, {tuple(scales.shape)} do not fit")
+    x = x.contiguous()
+    B, S, Hkv, D = x.shape
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().awq_kv_quant_fp8(_ptr(x), _ptr(cache), _ptr(scales), B, S, Hkv, D, cache.shape[1], int(start_pos),
+                                               _stream()), "awq_kv_quant_fp8")
+
+
+def kv_dequant_fp8(cache, scales, n, batch=None):
+    """Rows [0, n) of the first `batch` sequences (default: all) of an fp8 cache -> fp16 [batch, n, Hkv, 128] =
+    fp16(code * scale), saturated to +-65504 (awq_kv_dequant_fp8)."""
+    _require_gpu(cache, scales)
+    if cache.dtype != torch.uint8 or scales.dtype != torch.float32 or cache.dim() != 4 \
+            or tuple(scales.shape) != tuple(cache.shape[:3]) or not (cache.is_contiguous() and scales.is_contiguous()):
+        raise _lib.AwqHipError("kv_dequant_fp8 expects a contiguous uint8 cache [B, Tmax, Hkv, 128] and fp32 scales [B, Tmax, Hkv]")
+    B = cache.shape[0] if batch is None else int(batch)
+    if B > cache.shape[0]:
+        raise _lib.AwqHipError(f"kv_dequant_fp8: batch {B} > cache batch {cache.shape[0]}")
+    out = torch.empty((B, int(n), cache.shape[2], cache.shape[3]), dtype=torch.float16, device=cache.device)
+    with torch.cuda.device(cache.device):
+        _lib.check(_lib.lib().awq_kv_dequant_fp8(_ptr(cache), _ptr(scales), _ptr(out), B, int(n), cache.shape[2], cache.shape[3],
+                                                 cache.shape[1], _stream()), "awq_kv_dequant_fp8")
     return out
 
 

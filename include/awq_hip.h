@@ -474,6 +474,58 @@ AWQ_EXPORT int awq_decode_attention_rope_rows(const uint16_t* qkv, uint16_t* k_c
                                               int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale,
                                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- fp8 KV cache (opt-in: QuantAttentionFused(kv_cache_dtype="fp8")) ---------------------------------------------------
+ * Format.  The caches keep the layout [B, max_seq, n_kv_heads, 128] but hold one OCP e4m3fn code per value (uint8; MI300's
+ * fnuz format is NOT used), and k_scale / v_scale [B, max_seq, n_kv_heads] fp32 hold one scale per (sequence, row, KV head):
+ *   s = 2^k, k the smallest integer with amax <= 448 * 2^k, amax = max |x| over the row's 128 values (k taken exactly from the
+ *       exponent and mantissa bits of amax; a power of two makes scaling and dequantisation exact in fp32);
+ *   code = RNE_e4m3(x * 2^-k), clamped to +-448; x is the fp16 value the fp16 path would store (rotated k rounded to fp16, v);
+ *   a row of zeros: s = 0, codes 0; a row holding a NaN or an inf: s = NaN, codes 0 -- every read of it is NaN;
+ *   value = code * s (exact); dequantisation to fp16 (prefill) = fp16(code * s) saturated to +-65504 (NaN stays NaN).
+ * Rows cost 128 + 4 bytes instead of 256.  tests/kv8_ref.py restates the format in numpy.
+ * The *_fp8 entry points are the fp16 entry points above with uint8 caches and the scale arrays; same contracts otherwise.
+ * head_dim must be 128 (AWQ_ERR_UNSUPPORTED), k_scale / v_scale non-NULL (AWQ_ERR_NULL), caches 16-byte aligned and scales
+ * 4-byte aligned (AWQ_ERR_BAD_ALIGNMENT).  The fused forms quantize the new token themselves and attend to the quantized
+ * values, so they equal append + plain bit for bit. */
+AWQ_EXPORT int awq_rope_kv_append_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k_cache, uint8_t* v_cache, float* k_scale,
+                                      float* v_scale, const float* cos_table, const float* sin_table, const int32_t* pos_dev,
+                                      int64_t start_pos, int64_t B, int64_t S, int64_t n_heads, int64_t n_kv_heads,
+                                      int64_t head_dim, int64_t rotary_dim, int64_t max_seq, void* stream);
+AWQ_EXPORT int awq_rope_kv_append_rows_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k_cache, uint8_t* v_cache,
+                                           float* k_scale, float* v_scale, const float* cos_table, const float* sin_table,
+                                           const int32_t* pos_rows, int64_t B, int64_t S, int64_t n_heads, int64_t n_kv_heads,
+                                           int64_t head_dim, int64_t rotary_dim, int64_t max_seq, void* stream);
+AWQ_EXPORT int awq_decode_attention_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache, const float* k_scale,
+                                        const float* v_scale, uint16_t* out, const int32_t* len_dev, int64_t seq_len,
+                                        int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim,
+                                        int64_t max_seq, float scale, void* workspace, size_t workspace_bytes, void* stream);
+AWQ_EXPORT int awq_decode_attention_ex_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache,
+                                           const float* k_scale, const float* v_scale, uint16_t* out, const int32_t* len_dev,
+                                           int64_t seq_len, int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads,
+                                           int64_t head_dim, int64_t max_seq, float scale, float softcap,
+                                           const float* alibi_slopes, void* workspace, size_t workspace_bytes, void* stream);
+AWQ_EXPORT int awq_decode_attention_rope_fp8(const uint16_t* qkv, uint8_t* k_cache, uint8_t* v_cache, float* k_scale,
+                                             float* v_scale, const float* cos_table, const float* sin_table, uint16_t* out,
+                                             const int32_t* pos_dev, int64_t start_pos, int64_t max_len, int64_t B,
+                                             int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale,
+                                             void* workspace, size_t workspace_bytes, void* stream);
+AWQ_EXPORT int awq_decode_attention_rows_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache,
+                                             const float* k_scale, const float* v_scale, uint16_t* out, const int32_t* len_rows,
+                                             int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim,
+                                             int64_t max_seq, float scale, float softcap, const float* alibi_slopes,
+                                             void* workspace, size_t workspace_bytes, void* stream);
+AWQ_EXPORT int awq_decode_attention_rope_rows_fp8(const uint16_t* qkv, uint8_t* k_cache, uint8_t* v_cache, float* k_scale,
+                                                  float* v_scale, const float* cos_table, const float* sin_table, uint16_t* out,
+                                                  const int32_t* pos_rows, int64_t max_len, int64_t B, int64_t n_heads,
+                                                  int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale,
+                                                  void* workspace, size_t workspace_bytes, void* stream);
+/* x [B, S, n_kv_heads, 128] fp16 -> codes / scales of cache rows [start_pos, start_pos + S) of every sequence b < B. */
+AWQ_EXPORT int awq_kv_quant_fp8(const uint16_t* x, uint8_t* cache, float* scales, int64_t B, int64_t S, int64_t n_kv_heads,
+                                int64_t head_dim, int64_t max_seq, int64_t start_pos, void* stream);
+/* cache rows [0, n) of sequences b < B -> out [B, n, n_kv_heads, 128] fp16 (the prefill workspace). */
+AWQ_EXPORT int awq_kv_dequant_fp8(const uint8_t* cache, const float* scales, uint16_t* out, int64_t B, int64_t n,
+                                  int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, void* stream);
+
 /* ---- one-shot small-message all-reduce for tensor-parallel decode (no reference counterpart: SURVEY.md 2.3 / 8e) ------
  * out[i] = sum over ranks of in_r[i], fp16 with fp32 accumulation in rank order (bitwise identical on every rank), for the
  * [M, hidden] outputs of row-parallel projections (n_halfs % 4 == 0, n_halfs <= max_halfs; <= 64 KiB is what it is built for).

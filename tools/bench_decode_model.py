@@ -13,7 +13,7 @@ sys.path.insert(0, ROOT)
 H, I, V, HEADS, G = 4096, 11008, 32000, 32, 128
 
 
-def build_model(layers, max_ctx, dev, layout="gemm", hidden=H, inter=I, vocab=V, heads=HEADS):
+def build_model(layers, max_ctx, dev, layout="gemm", hidden=H, inter=I, vocab=V, heads=HEADS, kv_cache_dtype="fp16"):
     """The synthetic fused model: random int4 layers of the given shape, a cache window of max_ctx rows.
     Returns (lm, blocks, generator)."""
     from autoawq_amd.fuser import FusedCausalLM
@@ -49,7 +49,8 @@ def build_model(layers, max_ctx, dev, layout="gemm", hidden=H, inter=I, vocab=V,
     for _ in range(layers):
         mlp = QuantFusedMLP(rand_linear(H, I), rand_linear(I, H), rand_linear(H, I))
         blocks.append(LlamaLikeBlock(H, HEADS, HEADS, rand_linear(H, 3 * H), rand_linear(H, H), mlp,
-                                     FasterTransformerRMSNorm(ones(), 1e-5), FasterTransformerRMSNorm(ones(), 1e-5), dev, max_ctx))
+                                     FasterTransformerRMSNorm(ones(), 1e-5), FasterTransformerRMSNorm(ones(), 1e-5), dev, max_ctx,
+                                     kv_cache_dtype=kv_cache_dtype))
     emb = nn.Embedding(V, H).half().to(dev)
     head = nn.Linear(H, V, bias=False).half().to(dev)
     lm = FusedCausalLM(LlamaLikeModel(V, blocks, emb, FasterTransformerRMSNorm(ones(), 1e-5)), head)
@@ -57,7 +58,7 @@ def build_model(layers, max_ctx, dev, layout="gemm", hidden=H, inter=I, vocab=V,
 
 
 def run(layers=32, contexts=(64, 512, 2048), batch=1, steps=64, dev=None, verbose=True, check=True, layout="gemm",
-        hidden=H, inter=I, vocab=V, heads=HEADS):
+        hidden=H, inter=I, vocab=V, heads=HEADS, kv_cache_dtype="fp16"):
     """Returns {context: ms_per_token}.  check: before timing, the logits of the five-launch stream path (norms folded
     into the projections, fused RoPE + append + attention) must agree with the plain module path (separate norm, RoPE /
     append, attention, o_proj, MLP launches) on the same weights and cache."""
@@ -65,15 +66,24 @@ def run(layers=32, contexts=(64, 512, 2048), batch=1, steps=64, dev=None, verbos
 
     dev = dev or torch.device("cuda")
     H, I, V, HEADS = hidden, inter, vocab, heads  # (tests run a small stack through the same code)
-    lm, blocks, gen = build_model(layers, max(contexts) + steps + 8, dev, layout, hidden, inter, vocab, heads)
+    lm, blocks, gen = build_model(layers, max(contexts) + steps + 8, dev, layout, hidden, inter, vocab, heads, kv_cache_dtype)
     from autoawq_amd.modules.fused.decode import GraphedDecoder
 
     dec = GraphedDecoder(lm, batch=batch)  # one hipGraph per length bucket (256 / 1024 / 4096 ... rows); positions on the device
     tok = torch.randint(0, V, (batch, 1), device=dev, generator=gen)
     out = {}
     for blk in blocks:  # pretend a context is cached: random K / V rows
-        blk.attn.cache.k.normal_(generator=gen)
-        blk.attn.cache.v.normal_(generator=gen)
+        c = blk.attn.cache
+        if c.dtype == "fp8":  # the same random rows, quantized into codes + scales
+            from autoawq_amd import ops
+
+            for codes, scales in ((c.k, c.k_scale), (c.v, c.v_scale)):
+                for b in range(codes.shape[0]):
+                    rows = torch.empty(codes.shape[1:], dtype=torch.float16, device=dev).normal_(generator=gen)
+                    ops.kv_quant_fp8(rows[None], codes[b:b + 1], scales[b:b + 1])
+        else:
+            c.k.normal_(generator=gen)
+            c.v.normal_(generator=gen)
     if check:
         dec.seek(40)
         fused = dec.step(tok).float().clone()          # captured + replayed: the path that is timed below
@@ -131,5 +141,6 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--layout", choices=["gemm", "gemv"], default="gemm")
+    ap.add_argument("--kv-cache-dtype", choices=["fp16", "fp8"], default="fp16")
     a = ap.parse_args()
-    run(a.layers, tuple(int(c) for c in a.contexts.split(",")), a.batch, a.steps, layout=a.layout)
+    run(a.layers, tuple(int(c) for c in a.contexts.split(",")), a.batch, a.steps, layout=a.layout, kv_cache_dtype=a.kv_cache_dtype)

@@ -26,12 +26,12 @@ def _proc_tag(rp, mnt):
     return f" rp={rp:g} mnt={mnt}"
 
 
-def bench_generate(layers=32, contexts=(64, 2048), batches=(1, 4), new=128, rp=1.0, mnt=0):
+def bench_generate(layers=32, contexts=(64, 2048), batches=(1, 4), new=128, rp=1.0, mnt=0, kv_cache_dtype="fp16"):
     import bench_decode_model
     from autoawq_amd.modules.fused.decode import GraphedDecoder
 
     dev = torch.device("cuda")
-    lm, blocks, gen = bench_decode_model.build_model(layers, max(contexts) + new + 8, dev, layout="gemv")
+    lm, blocks, gen = bench_decode_model.build_model(layers, max(contexts) + new + 8, dev, layout="gemv", kv_cache_dtype=kv_cache_dtype)
     V = bench_decode_model.V
     rows = []
     for B in batches:
@@ -79,7 +79,7 @@ def _left_padded(prompts, dev):
     return ids, mask
 
 
-def bench_ragged(layers=32, batches=(4, 8), new=128, shortest=64, longest=2048):
+def bench_ragged(layers=32, batches=(4, 8), new=128, shortest=64, longest=2048, kv_cache_dtype="fp16"):
     """Prompts spread evenly between `shortest` and `longest` tokens.  'ragged' = one generate call with the attention_mask
     (per-row positions); 'one at a time' = each prompt through a batch-1 decoder, times summed; 'uniform padded' = the padded
     batch without a mask (every row at the longest context: what per-row lengths save -- its tokens are NOT correct for the
@@ -88,7 +88,7 @@ def bench_ragged(layers=32, batches=(4, 8), new=128, shortest=64, longest=2048):
     from autoawq_amd.modules.fused.decode import GraphedDecoder
 
     dev = torch.device("cuda")
-    lm, blocks, gen = bench_decode_model.build_model(layers, longest + new + 8, dev, layout="gemv")
+    lm, blocks, gen = bench_decode_model.build_model(layers, longest + new + 8, dev, layout="gemv", kv_cache_dtype=kv_cache_dtype)
     V = bench_decode_model.V
     rows = []
 
@@ -175,10 +175,11 @@ if __name__ == "__main__":
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--repetition-penalty", type=float, default=1.0)
     ap.add_argument("--min-new-tokens", type=int, default=0)
+    ap.add_argument("--kv-cache-dtype", choices=["fp16", "fp8"], default="fp16")
     a = ap.parse_args()
     if a.sampler_only:
         bench_sampler(rp=a.repetition_penalty, mnt=a.min_new_tokens)
     elif a.ragged:
-        bench_ragged(layers=a.layers, new=a.new)
+        bench_ragged(layers=a.layers, new=a.new, kv_cache_dtype=a.kv_cache_dtype)
     else:
-        bench_generate(layers=a.layers, new=a.new, rp=a.repetition_penalty, mnt=a.min_new_tokens)
+        bench_generate(layers=a.layers, new=a.new, rp=a.repetition_penalty, mnt=a.min_new_tokens, kv_cache_dtype=a.kv_cache_dtype)
