@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_bound
 from conftest import GOLDEN, golden
 from test_checkpoint import ckpt, skeleton
 
@@ -268,6 +269,9 @@ def test_decode_attention_vs_oracle(ops, B, Hq, Hkv, T):
     ln = torch.tensor([T], dtype=torch.int32, device="cuda")  # device-side length, launch sized for the whole cache
     got2 = ops.decode_attention(q.cuda(), kc.cuda(), vc.cuda(), 1, len_dev=ln, max_len=Tmax).cpu().numpy().astype(np.float64)
     assert np.abs(got2 - want).max() <= 2e-3 * np.abs(want).max() + 2 ** -11
+    for g, n in ((got, T), (got2, Tmax)):  # the derived per-element bound (tests/attn_bound.py) of the launch's split count
+        w, bound = attn_bound.decode_bound(q, kc, vc, [T] * B, attn_bound.decode_splits(n, B, Hq, Hkv))
+        attn_bound.assert_attention_close(torch.from_numpy(g), w, bound, f"max_len {n}")
 
 
 @pytest.mark.gpu
@@ -290,6 +294,10 @@ def test_decode_attention_softcap_and_alibi_vs_oracle(ops, B, Hq, Hkv, T, softca
     ln = torch.tensor([T], dtype=torch.int32, device="cuda")
     got2 = ops.decode_attention(q.cuda(), kc.cuda(), vc.cuda(), 1, len_dev=ln, max_len=Tmax, softcap=softcap, alibi_slopes=sl)
     assert np.abs(got2.cpu().numpy().astype(np.float64) - want).max() <= 2e-3 * np.abs(want).max() + 2 ** -11
+    for g, n in ((torch.from_numpy(got), T), (got2, Tmax)):  # the derived per-element bound, on the fp32 slopes the kernel reads
+        w, bound = attn_bound.decode_bound(q, kc, vc, [T] * B, attn_bound.decode_splits(n, B, Hq, Hkv), softcap=softcap,
+                                           alibi=sl.cpu() if alibi else None)
+        attn_bound.assert_attention_close(g.cpu(), w, bound, f"max_len {n}")
     plain = decoder_oracle.attention_reference(q.numpy(), kc.numpy(), vc.numpy(), T)
     if T > 1:
         assert np.abs(plain - want).max() > 1e-3, "the modifiers must change the result for this test to mean anything"
@@ -359,6 +367,9 @@ def test_prefill_attention_vs_oracle(ops, B, S, Hq, Hkv, start, softcap, alibi):
     full = torch.matmul(torch.softmax(sc, dim=-1), vf).transpose(1, 2)
     d = (out.float() - full).abs()
     assert bool((d <= 2e-3 * full.abs().amax(dim=-1, keepdim=True) + 2e-3).all()), float(d.max())
+    # every output element against the fp64 reference within the derived prefill bound (tests/attn_bound.py)
+    w, bound = attn_bound.prefill_bound(qd, kd, vd, start, softcap=softcap, alibi=slopes.cuda() if alibi else None)
+    attn_bound.assert_attention_close(out, w, bound, "prefill")
 
 
 @pytest.mark.gpu

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import attn_bound
 import kv8_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -152,6 +153,11 @@ def test_decode_attention_vs_oracle(ops, G, form):
             want = decoder_oracle.attention_reference(q.numpy()[b:b + 1], kd[b:b + 1], vd[b:b + 1], L, softcap=softcap,
                                                       alibi_slopes=slopes)
             assert np.abs(got[b:b + 1] - want).max() <= 2e-3 * np.abs(want).max() + 2 ** -11, (G, form, T, b)
+        # the derived per-element bound (tests/attn_bound.py) on the dequantised cache, split count of the launch
+        splits = attn_bound.decode_splits(Tmax if rows else T, B, Hq, Hkv)
+        w, bound = attn_bound.decode_bound(q, torch.from_numpy(kd), torch.from_numpy(vd), lens, splits, softcap=softcap,
+                                           alibi=None if slopes is None else torch.from_numpy(slopes).float())
+        attn_bound.assert_attention_close(torch.from_numpy(got), w, bound, f"{form} G {G} T {T}")
 
 
 @pytest.mark.parametrize("G", [1, 2, 4, 8])

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import attn_bound
+
 pytestmark = pytest.mark.gpu
 
 TMAX = 1024
@@ -62,6 +64,9 @@ def test_decode_attention_rows_equals_each_row_alone(ops, G, softcap, alibi, max
         want = decoder_oracle.attention_reference(q[b:b + 1].cpu().numpy(), kc[b:b + 1].cpu().numpy(),
                                                   vc[b:b + 1].cpu().numpy(), n, softcap=softcap, alibi_slopes=slopes)
         _close(got[b:b + 1].cpu().numpy().astype(np.float64), want)
+        w, bound = attn_bound.decode_bound(q[b:b + 1], kc[b:b + 1], vc[b:b + 1], [n], attn_bound.decode_splits(max_len, B, Hq, HKV),
+                                           softcap=softcap, alibi=sl)
+        attn_bound.assert_attention_close(got[b:b + 1], w, bound, f"row {b} length {n}")
 
 
 @pytest.mark.parametrize("G", GROUPS)
@@ -85,6 +90,8 @@ def test_decode_attention_rope_rows_equals_each_row_alone(ops, G):
         q = ops.rope_kv_append(qkv[b:b + 1], ka.clone(), va.clone(), rope.cos, rope.sin, p, Hq, HKV, 128, 128)
         want = decoder_oracle.attention_reference(q[:, 0].cpu().numpy(), ka.cpu().numpy(), va.cpu().numpy(), p + 1)
         _close(got[b:b + 1].cpu().numpy().astype(np.float64), want)
+        w, bound = attn_bound.decode_bound(q[:, 0], ka, va, [p + 1], attn_bound.decode_splits(TMAX, B, Hq, HKV))
+        attn_bound.assert_attention_close(got[b:b + 1], w, bound, f"row {b} position {p}")
 
 
 @pytest.mark.parametrize("rot", [128, 64])
@@ -126,6 +133,8 @@ def test_short_rows_in_a_long_bucket_leave_empty_splits(ops):
     for b, n in enumerate(lens):
         single = ops.decode_attention(q[b:b + 1], kc[b:b + 1], vc[b:b + 1], n)
         assert (got[b:b + 1].float() - single.float()).abs().max().item() <= 2e-3 * single.float().abs().max().item() + 2 ** -11
+        w, bound = attn_bound.decode_bound(q[b:b + 1], kc[b:b + 1], vc[b:b + 1], [n], attn_bound.decode_splits(4096, B, Hq, HKV))
+        attn_bound.assert_attention_close(got[b:b + 1], w, bound, f"row {b} length {n} of a 4096 bucket")
 
 
 def test_argument_checks(ops):
