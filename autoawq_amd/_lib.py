@@ -58,6 +58,20 @@ class AwqSampleProcArgs(ctypes.Structure):
                 ("history_stride", c_int64)]
 
 
+class AwqSpecParams(ctypes.Structure):
+    """struct AwqSpecParams of include/awq_hip.h (same field order; lives in device memory)."""
+    _fields_ = [("n_eos", ctypes.c_int32), ("pad", ctypes.c_int32), ("max_new_tokens", ctypes.c_int32),
+                ("ngram_max", ctypes.c_int32), ("eos", ctypes.c_int32 * 8)]
+
+
+class AwqSpecArgs(ctypes.Structure):
+    """struct AwqSpecArgs of include/awq_hip.h (same field order)."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("B", c_int64), ("T", c_int64), ("params", c_void_p),
+                ("tok", c_void_p), ("pred", c_void_p), ("hist", c_void_p), ("hist_cap", c_int64), ("n_hist", c_void_p),
+                ("cnt", c_void_p), ("ring", c_void_p), ("ring_cap", c_int64), ("finished", c_void_p), ("pos_rows", c_void_p),
+                ("len_rows", c_void_p), ("status", c_void_p), ("steps", c_void_p), ("stream", c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol include/awq_hip.h declares
 # (tests/test_boundary.py cross-checks this table against the header and the .so).
 SIGNATURES = {
@@ -135,6 +149,11 @@ SIGNATURES = {
     "awq_sample_tokens": (c_int, [ctypes.POINTER(AwqSampleArgs)]),
     "awq_sample_tokens_ex": (c_int, [ctypes.POINTER(AwqSampleArgs), ctypes.POINTER(AwqSampleProcArgs)]),
     "awq_sample_history_seed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "awq_verify_attention_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "awq_verify_attention_splits": (c_int, [c_int64] * 5),
+    "awq_verify_attention_rows": (c_int, [c_void_p] * 5 + [c_int64] * 7 + [c_float, c_void_p, c_size_t, c_void_p]),
+    "awq_spec_accept": (c_int, [ctypes.POINTER(AwqSpecArgs)]),
+    "awq_ngram_draft": (c_int, [ctypes.POINTER(AwqSpecArgs)]),
 }
 
 

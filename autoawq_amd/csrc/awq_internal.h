@@ -176,3 +176,10 @@ int awq_launch_kv_quant_fp8(const uint16_t* x, uint8_t* codes, float* scales, in
                             hipStream_t st);
 int awq_launch_kv_dequant_fp8(const uint8_t* codes, const float* scales, uint16_t* out, int B, int n, int Hkv, int Tmax,
                               hipStream_t st);
+
+// verify_attn.hip: attention of T = 2 .. 8 new tokens per sequence over the cache at per-row device positions (speculative decoding)
+int awq_verify_attention_splits_impl(int max_len, int B, int T, int Hq, int Hkv);
+size_t awq_verify_attention_workspace_bytes_impl(int B, int T, int Hq, int splits);
+int awq_launch_verify_attention(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
+                                const int32_t* pos_rows, int max_len, int B, int T, int Hq, int Hkv, int D, int Tmax, float scale,
+                                void* workspace, size_t workspace_bytes, hipStream_t st);

@@ -741,6 +741,35 @@ int awq_decode_attention_rope_rows(const uint16_t* qkv, uint16_t* k_cache, uint1
                                        cos_table, sin_table, static_cast<hipStream_t>(stream), 0.f, nullptr, true);
 }
 
+// ---- speculative decoding (verify_attn.hip): T new tokens per sequence at per-row device positions
+size_t awq_verify_attention_workspace_bytes(int64_t B, int64_t T, int64_t n_heads) {
+    if (B <= 0 || T <= 0 || n_heads <= 0 || B * T * n_heads > INT32_MAX / 64) return 0;
+    return awq_verify_attention_workspace_bytes_impl((int)B, (int)T, (int)n_heads, 64);
+}
+
+int awq_verify_attention_splits(int64_t max_len, int64_t B, int64_t T, int64_t n_heads, int64_t n_kv_heads) {
+    if (max_len < 1 || max_len > INT32_MAX || B < 1 || B > 65535 || T < 2 || T > 8 || n_heads < 1 || n_kv_heads < 1 ||
+        n_kv_heads > 65535 || n_heads % n_kv_heads)
+        return AWQ_ERR_BAD_SHAPE;
+    return awq_verify_attention_splits_impl((int)max_len, (int)B, (int)T, (int)n_heads, (int)n_kv_heads);
+}
+
+int awq_verify_attention_rows(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
+                              const int32_t* pos_rows, int64_t max_len, int64_t B, int64_t T, int64_t n_heads, int64_t n_kv_heads,
+                              int64_t head_dim, int64_t max_seq, float scale, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    if (B < 0 || B > 65535 || n_heads < 1 || n_heads > 65535 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq < 1 ||
+        max_seq > INT32_MAX || max_len < 0 || max_len > INT32_MAX)
+        return AWQ_ERR_BAD_SHAPE;
+    if (T < 2 || T > 8) return AWQ_ERR_UNSUPPORTED;
+    if (B == 0) return AWQ_OK;
+    if (!q || !k_cache || !v_cache || !out || !pos_rows) return AWQ_ERR_NULL;
+    if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
+    return awq_launch_verify_attention(q, k_cache, v_cache, out, pos_rows, (int)max_len, (int)B, (int)T, (int)n_heads,
+                                       (int)n_kv_heads, (int)head_dim, (int)max_seq, scale, workspace, workspace_bytes,
+                                       static_cast<hipStream_t>(stream));
+}
+
 // ---- fp8 KV cache (decoder.hip, KV8): same checks as the fp16 entry points, plus head_dim == 128 and the scale arrays
 static int kv8_check(const void* kc, const void* vc, const float* ks, const float* vs, int64_t head_dim) {
     if (!kc || !vc || !ks || !vs) return AWQ_ERR_NULL;

@@ -31,6 +31,11 @@ class FusedCausalLM(nn.Module):
     def forward(self, input_ids):
         return self.lm_head(self.model(input_ids).last_hidden_state)
 
+    @torch.inference_mode()
+    def verify(self, input_ids):
+        """[B, T] ids -> [B, T, vocab]: the verify step of speculative decoding (LlamaLikeModel.forward(verify=True))"""
+        return self.lm_head(self.model(input_ids, verify=True).last_hidden_state)
+
 
 def _layout_of(model):
     kinds = {type(m) for m in model.modules() if isinstance(m, (WQLinear_GEMM, WQLinear_GEMV))}

@@ -132,6 +132,7 @@ class QuantAttentionFused(nn.Module):
         self._pos_dev = None
         self._len_dev = None
         self._per_row = False
+        self.verify_rows = False  # set by the caller of a speculative verify step (LlamaLikeModel.forward(verify=True))
 
     def use_device_positions(self, pos_dev, len_dev, per_row=False):
         """pos_dev / len_dev: int32 device tensors of one element (shared by all layers) holding the
@@ -196,6 +197,28 @@ class QuantAttentionFused(nn.Module):
         scores = scores.masked_fill(kpos > qpos, float("-inf"))
         return torch.matmul(torch.softmax(scores, dim=-1), v.float()).to(torch.float16)
 
+    def _verify_qkv(self, xqkv, apply_o_proj):
+        """The verify step of speculative decoding (asked for explicitly through `verify_rows`, never inferred from seqlen, so
+        chunked prefill keeps its meaning): T = 2 .. 8 new tokens per sequence at the per-row device positions.  Rows
+        pos_b .. pos_b + T - 1 are appended, query (b, j) attends over rows <= pos_b + j (ops.verify_attention_rows).  The
+        host-side start_pos is not advanced: the decoder owns the positions and keeps only the rows it accepts."""
+        bsz, seqlen, _ = xqkv.shape
+        if self.kv_cache_dtype == "fp8":
+            raise NotImplementedError('speculative decoding: kv_cache_dtype="fp8" is not supported (verify_attention_rows '
+                                      "reads fp16 caches)")
+        if not (self._per_row and self._pos_dev is not None):
+            raise RuntimeError("a verify step needs per-row device positions (use_device_positions(..., per_row=True))")
+        native = self.head_dim == 128 and self.n_kv_groups in (1, 2, 4, 8)
+        if not native or self.alibi is not None or self.attn_logit_softcapping > 0 or not 2 <= seqlen <= 8:
+            raise NotImplementedError("a verify step takes 2 .. 8 tokens, head_dim 128, 1, 2, 4 or 8 query heads per KV head, "
+                                      "no ALiBi and no soft cap")
+        xq = ops.rope_kv_append(xqkv, self.cache.k, self.cache.v, self.rope.cos, self.rope.sin, 0, self.n_heads, self.n_kv_heads,
+                                self.head_dim, self.rotary_dim, pos_rows=self._pos_dev)
+        out = ops.verify_attention_rows(xq, self.cache.k, self.cache.v, self._pos_dev, max_len=max(seqlen, self._len_bound()))
+        heads = out.reshape(bsz, seqlen, -1)
+        attn_output = self.o_proj(heads) if apply_o_proj else heads
+        return attn_output, heads, [torch.zeros(1, 1, self.start_pos, 1)]
+
     def forward_qkv(self, xqkv, apply_o_proj=True):
         """Everything after the qkv projection (the caller may have produced `xqkv` [B, S, (Hq + 2 Hkv) D]
         with the norm folded into the projection).  apply_o_proj=False returns the attention heads' output
@@ -203,6 +226,8 @@ class QuantAttentionFused(nn.Module):
         bsz, seqlen, _ = xqkv.shape
         self._resize_cache(bsz)
         xqkv = self._qkv_rows(xqkv)
+        if self.verify_rows:
+            return self._verify_qkv(xqkv, apply_o_proj)
         device_pos = self._pos_dev is not None and seqlen == 1
         rows = device_pos and self._per_row  # one position / length word per sequence: the *_rows kernels
         # the hand-written decode kernels take head_dim 128 and 1, 2, 4 or 8 query heads per KV head; other

@@ -38,6 +38,18 @@ an all-ones mask, takes the shared words and the graphs above unchanged.
 repetition_penalty / min_new_tokens (transformers' logit processors) run inside the sampler's passes, reading a per-row bitmap of
 the ids seen so far that the sampler itself extends: a third and fourth family of generation graphs (`proc_gen_graphs`,
 `row_proc_gen_graphs`).  With both at their defaults generate takes the graphs above, unchanged.
+
+Speculative decoding (`generate(draft_tokens=K)`, `verify` / `advance_rows`): one pass over the weights for T = K + 1 tokens per
+row.  A graph of the family `spec_graphs[(bound, T)]` runs the model on tok [B, T] at the per-row positions (rope + append of T
+rows, csrc/verify_attn.hip), takes the greedy argmax of every slot with the sampler, keeps the longest run of drafts the model
+agrees with (awq_spec_accept: ring, history, positions and finished flags advance on the device by what was accepted) and
+writes the next step's drafts by prompt lookup in the row's own history (awq_ngram_draft).  Rejected drafts leave cache rows at
+and above the row's new position; the next step's append overwrites them, nothing is rolled back.  The host only bounds the
+positions between checks.  `verify_graphs[(bound, T)]` is the same step without the two integer kernels, for callers with
+drafts of their own.  draft_tokens=0 (the default) creates none of this.
+
+    out = dec.generate(ids, max_new_tokens=128, draft_tokens=3, draft_ngram=3)   # the text of the plain greedy run
+    dec.last_spec                                                                 # {"replays": r, "new_tokens": [n_b ...]}
 """
 import torch
 
@@ -87,6 +99,11 @@ class GraphedDecoder:
         self.proc_gen_graphs = {}  # with the logit processors (repetition_penalty / min_new_tokens): keyed as gen_graphs
         self.row_proc_gen_graphs = {}  # ... and as row_gen_graphs
         self._gen = None  # generate's device words (allocated by its first call)
+        self.spec_graphs = {}    # speculative decoding: (bucket bound, T) -> (graph, logits): verify step + argmax + accept + draft
+        self.verify_graphs = {}  # (bucket bound, T) -> (graph, logits): the verify step alone (`verify`)
+        self._spec = {}          # T -> the device words of the speculative path (allocated by its first use)
+        self._verify_T = None    # tokens appended by the last `verify`, until `advance_rows`
+        self.last_spec = None
         self.position = 0
         self.positions = None  # per-row mode: the host's position of every row (None: one shared position)
         for b in self.blocks:
@@ -314,10 +331,193 @@ class GraphedDecoder:
             raise AwqHipError(f"generate: rows {bad} produced NaN / +inf logits or kept no token")
         return bool(g["finished"].cpu().all())
 
+    # ---- speculative decoding --------------------------------------------------------------------------------------------
+    def _spec_check_model(self, T):
+        from .model import MixtralModel
+
+        if not 2 <= T <= 8:
+            raise ValueError(f"a verify step takes 2 .. 8 tokens per row (draft_tokens 1 .. 7), got {T}")
+        if self.batch * T > 1024:
+            raise ValueError(f"batch * (draft_tokens + 1) = {self.batch * T} exceeds the sampler's 1024 rows")
+        if any(b.attn.kv_cache_dtype == "fp8" for b in self.blocks):
+            raise NotImplementedError('speculative decoding: kv_cache_dtype="fp8" is not supported (the verify attention reads '
+                                      "fp16 caches)")
+        if isinstance(self.lm.model, MixtralModel):
+            raise NotImplementedError("speculative decoding: fuse_mixtral models are refused (the MoE block under a verify step "
+                                      "is not covered by tests)")
+
+    def _spec_state(self, T, vocab=None, ring_cap=0, hist_cap=0):
+        """The device words of the speculative path for steps of T tokens; their addresses are baked into the graphs of that T,
+        which are dropped when the words have to be reallocated (another vocabulary, a longer ring or history)."""
+        st = self._spec.get(T)
+        if st is not None and (vocab is None or st["vocab"] == vocab) and st["ring"].shape[1] >= ring_cap and st["hist"].shape[1] >= hist_cap:
+            return st
+        if vocab is None:
+            vocab = int(self.lm.model.vocab_size) if st is None else st["vocab"]
+        B, dev = self.batch, self.device
+        with torch.inference_mode(False):
+            st = {"vocab": vocab,
+                  "tok": torch.zeros((B, T), dtype=torch.int64, device=dev),
+                  "pred": torch.zeros(B * T, dtype=torch.int64, device=dev),
+                  "params": torch.zeros(48, dtype=torch.uint8, device=dev),         # struct AwqSpecParams
+                  "argmax_params": ops.sample_params(do_sample=False).to(dev),      # the slots' argmax: greedy, no EOS ids
+                  "t": torch.ones(1, dtype=torch.int32, device=dev),
+                  "status": torch.zeros((B * T + 31) // 32, dtype=torch.int32, device=dev),
+                  "ws": torch.zeros(ops.sample_workspace_bytes(B * T, vocab), dtype=torch.uint8, device=dev),
+                  "hist": torch.zeros((B, max(int(hist_cap), 256)), dtype=torch.int32, device=dev),
+                  "n_hist": torch.zeros(B, dtype=torch.int32, device=dev),
+                  "cnt": torch.zeros(B, dtype=torch.int32, device=dev),
+                  "ring": torch.zeros((B, max(int(ring_cap), 256)), dtype=torch.int32, device=dev),
+                  "finished": torch.zeros(B, dtype=torch.int32, device=dev),
+                  "steps": torch.zeros(B, dtype=torch.int32, device=dev)}
+        self.spec_graphs = {k: v for k, v in self.spec_graphs.items() if k[1] != T}
+        self.verify_graphs = {k: v for k, v in self.verify_graphs.items() if k[1] != T}
+        self._spec[T] = st
+        return st
+
+    def _spec_tail(self, st, logits):
+        """the greedy argmax of the B * T slots: the sampler itself (its tie and NaN / +inf rules), no ring, no flags, no EOS ids"""
+        ops.sample_launch(logits.view(-1, logits.shape[-1]), st["argmax_params"], st["t"], st["pred"], st["status"], st["ws"],
+                          greedy=True)
+
+    @torch.inference_mode()
+    def _capture_spec(self, bound, T, full):
+        st = self._spec[T]
+        for b in self.blocks:
+            b.attn.use_device_positions(self.pos_rows, self.len_rows, per_row=True)
+            b.attn.decode_len_bound = bound
+        caller = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self.stream):
+            self.stream.wait_stream(caller)
+            # warm-up outside the capture: the model and the argmax only -- they append T rows at and above the rows' positions,
+            # which the first replay writes again; the integer kernels move the decoder's words and run in replays alone
+            logits = self.lm.verify(st["tok"])
+            if full:
+                self._spec_tail(st, logits)
+            self.stream.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=self.stream):
+                logits = self.lm.verify(st["tok"])
+                if full:
+                    self._spec_tail(st, logits)
+                    ops.spec_accept(st["params"], st["tok"], st["pred"], st["hist"], st["n_hist"], st["cnt"], st["ring"],
+                                    st["finished"], self.pos_rows, self.len_rows, status=st["status"], steps=st["steps"])
+                    ops.ngram_draft(st["params"], st["tok"], st["hist"], st["n_hist"])
+            self.stream.synchronize()
+        caller.wait_stream(self.stream)
+        self._sync_host_state()
+        family = self.spec_graphs if full else self.verify_graphs
+        family[(bound, T)] = (graph, logits)
+        return family[(bound, T)]
+
+    def _replay_spec(self, bound, T, full):
+        family = self.spec_graphs if full else self.verify_graphs
+        graph, logits = family.get((bound, T)) or self._capture_spec(bound, T, full)
+        caller = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            graph.replay()
+        caller.wait_stream(self.stream)
+        return logits
+
+    @torch.inference_mode()
+    def verify(self, token_ids):
+        """token_ids [batch, T], T = 2 .. 8: row b's tokens at positions p_b .. p_b + T - 1 (its last token, then T - 1 drafts).
+        Returns the logits [batch, T, vocab] -- slot j is what `step` would return after the first j + 1 of them; the graph's
+        static buffer, overwritten by the next call.  T cache rows are appended per row and NOTHING advances: `advance_rows`
+        then says how many of them each row keeps.  Switches the decoder to per-row positions."""
+        token_ids = token_ids.to(self.device)
+        if token_ids.dim() != 2 or token_ids.shape[0] != self.batch:
+            raise ValueError(f"verify: token_ids must be [{self.batch}, T], got {tuple(token_ids.shape)}")
+        T = int(token_ids.shape[1])
+        self._spec_check_model(T)
+        if self.positions is None:
+            self.seek_rows([self.position] * self.batch)
+        if max(self.positions) + T > self.max_seq_len:
+            raise ValueError(f"verify: positions {self.positions} + {T} tokens run past the cache window {self.max_seq_len} "
+                             "(no window roll inside a speculative step)")
+        st = self._spec_state(T)
+        st["tok"].copy_(token_ids)
+        logits = self._replay_spec(self.bucket(max(self.positions) + T), T, full=False)
+        self._verify_T = T
+        return logits
+
+    def advance_rows(self, counts):
+        """After `verify`: row b keeps the first counts[b] of the T tokens it appended (1 <= counts[b] <= T); the rows of the
+        others lie at and above its new position and are overwritten by the next step."""
+        counts = [int(c) for c in counts]
+        if self._verify_T is None:
+            raise RuntimeError("advance_rows follows a verify call")
+        if len(counts) != self.batch or not all(1 <= c <= self._verify_T for c in counts):
+            raise ValueError(f"advance_rows: {self.batch} counts in 1 .. {self._verify_T} expected, got {counts}")
+        self._verify_T = None
+        self.seek_rows([p + c for p, c in zip(self.positions, counts)])
+
+    def _generate_spec(self, input_ids, max_new_tokens, K, ngram, eos, pad_token_id, check_every, attention_mask):
+        T = K + 1
+        self._spec_check_model(T)
+        B, S = input_ids.shape
+        ragged = self._ragged(input_ids, attention_mask)
+        starts, lengths = ragged if ragged is not None else ([0] * B, [S] * B)
+        if max(lengths) + max_new_tokens + T > self.max_seq_len:
+            raise ValueError(f"speculative generate: prompt ({max(lengths)}) + max_new_tokens ({max_new_tokens}) + {T} step tokens "
+                             f"exceed the cache window {self.max_seq_len} (no window roll inside a speculative run)")
+        pad = int(pad_token_id) if pad_token_id is not None else (eos[0] if eos else 0)
+        params = ops.spec_params(eos_ids=eos, pad=pad, max_new_tokens=max_new_tokens, ngram_max=ngram)
+        logits = self.prefill(input_ids, attention_mask if ragged is not None else None)
+        if ragged is not None:
+            last = torch.tensor([s + n - 1 for s, n in zip(starts, lengths)], dtype=torch.int64, device=self.device)
+            logits = logits[torch.arange(B, device=self.device), last].unsqueeze(1).contiguous()
+        else:
+            self.seek_rows(lengths)  # always per-row: equal positions diverge at the first step
+        st = self._spec_state(T, logits.shape[-1], max_new_tokens, max(lengths) + max_new_tokens)
+        first = ops.sample_tokens(logits, do_sample=False)  # token 1, eagerly (raises on NaN / +inf logits)
+        # reset the decoder-owned words outside any capture: prompt and token 1 into the history, token 1 into the ring
+        n_hist = torch.tensor(lengths, dtype=torch.int64, device=self.device)
+        st["params"].copy_(params)
+        st["status"].zero_()
+        st["ring"].zero_()
+        st["hist"].zero_()
+        st["hist"][:, :max(lengths)] = pack_ids(input_ids, starts, lengths).to(torch.int32)
+        st["hist"].scatter_(1, n_hist.view(-1, 1), first.to(torch.int32).view(-1, 1))
+        st["n_hist"].copy_((n_hist + 1).to(torch.int32))
+        st["ring"][:, 0] = first.to(torch.int32)
+        st["cnt"].fill_(1)
+        st["steps"].zero_()
+        hit = torch.zeros(B, dtype=torch.bool, device=self.device)
+        for e in eos:
+            hit |= first == e
+        st["finished"].copy_((hit | (max_new_tokens <= 1)).to(torch.int32))
+        ops.ngram_draft(st["params"], st["tok"], st["hist"], st["n_hist"])
+        upper, replays = list(lengths), 0
+        words = None
+        for _ in range(max_new_tokens - 1):  # every replay emits at least one token per unfinished row: the budget ends the run
+            if replays % check_every == 0:   # one copy: the flags, and the positions that make the host's bounds exact again
+                words = torch.cat([st["finished"], self.pos_rows]).cpu().tolist()
+                if all(words[:B]):
+                    break
+                upper = words[B:]
+            self._replay_spec(self.bucket(min(max(upper) + T, self.max_seq_len)), T, full=True)
+            upper = [u + T for u in upper]
+            replays += 1
+        words = torch.cat([st["finished"], self.pos_rows, st["cnt"], st["steps"], st["status"]]).cpu().tolist()
+        bad = sorted({r // T for r in range(B * T) if (words[4 * B + r // 32] >> (r % 32)) & 1})
+        if bad:
+            raise AwqHipError(f"generate: rows {bad} produced NaN / +inf logits")
+        cnt = words[2 * B:3 * B]
+        self.seek_rows(words[B:2 * B])
+        # replays: those the slowest row needed (the host may have launched a few more before its next look at the flags)
+        self.last_spec = {"replays": max(words[3 * B:4 * B]), "new_tokens": cnt, "launched": replays}
+        n = max(cnt)
+        new = st["ring"][:, :n].long()
+        keep = torch.arange(n, device=self.device).view(1, -1) < torch.tensor(cnt, device=self.device).view(-1, 1)
+        new = torch.where(keep, new, torch.full_like(new, pad))
+        return torch.cat([input_ids.long(), new], dim=1)
+
     @torch.inference_mode()
     def generate(self, input_ids, max_new_tokens, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                  eos_token_id=None, pad_token_id=None, check_every=16, attention_mask=None, repetition_penalty=1.0,
-                 min_new_tokens=0):
+                 min_new_tokens=0, draft_tokens=0, draft_ngram=3):
         """input_ids [batch, prompt] -> [batch, prompt + n] int64 on the device, n <= max_new_tokens; rows that emitted an EOS id
         are padded with pad_token_id (default: the first EOS id) from then on, and the run stops once every row has (HF's
         `generate` semantics).  The prompt is prefilled eagerly and token 1 sampled eagerly from its last position; every later
@@ -330,7 +530,13 @@ class GraphedDecoder:
         repetition_penalty (> 0, 1 = off) and min_new_tokens (>= 0, 0 = off): transformers' RepetitionPenaltyLogitsProcessor and
         MinNewTokensLengthLogitsProcessor, applied inside the sampler (ops.sample_tokens).  The penalty covers every id of
         input_ids as passed (pad columns included, as transformers' input_ids carry them) and every generated token (pads of
-        finished rows included), also after a window roll has dropped their cache rows."""
+        finished rows included), also after a window roll has dropped their cache rows.
+        draft_tokens = K in 1 .. 7 (0 = off): greedy speculative decoding by prompt lookup (transformers'
+        `prompt_lookup_num_tokens`) -- every replay verifies K drafts found by matching the row's last draft_ngram .. 1 tokens
+        earlier in its own text and emits 1 .. K + 1 tokens; the text is the plain greedy run's (up to ties the two launch shapes
+        round differently).  `last_spec` then holds {"replays": those the slowest row needed, "new_tokens": per row, "launched"}.  Greedy only (do_sample with temperature > 0,
+        repetition_penalty != 1 and min_new_tokens > 0 raise ValueError; an fp8 cache NotImplementedError), and no window roll:
+        prompt + max_new_tokens + K + 1 <= max_seq_len for every row."""
         input_ids = input_ids.to(self.device)
         if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
             raise ValueError(f"input_ids must be [{self.batch}, prompt], got {tuple(input_ids.shape)}")
@@ -338,6 +544,15 @@ class GraphedDecoder:
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+        if draft_tokens:
+            if isinstance(draft_tokens, bool) or int(draft_tokens) != draft_tokens or not 1 <= int(draft_tokens) <= 7:
+                raise ValueError(f"draft_tokens must be an integer in 0 .. 7, got {draft_tokens}")
+            if do_sample and float(temperature) > 0:
+                raise ValueError("speculative decoding is greedy: do_sample with temperature > 0 needs rejection sampling")
+            if float(repetition_penalty) != 1.0 or int(min_new_tokens) > 0:
+                raise ValueError("speculative decoding does not run the logit processors (repetition_penalty, min_new_tokens)")
+            return self._generate_spec(input_ids, max_new_tokens, int(draft_tokens), int(draft_ngram), eos, pad_token_id,
+                                       check_every, attention_mask)
         params = ops.sample_params(do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, eos_ids=eos,
                                    pad=pad_token_id)
         proc_bytes = ops.sample_proc_params(repetition_penalty, min_new_tokens)

@@ -80,10 +80,25 @@ class LlamaLikeModel(nn.Module):
                         and isinstance(b.norm_2, FasterTransformerRMSNorm) for b in self.blocks))
 
     @torch.inference_mode()
-    def forward(self, input_ids, *args, **kwargs):
+    def forward(self, input_ids, *args, verify=False, **kwargs):
+        """verify=True: the T-token verify step of speculative decoding (modules/fused/decode.py).  [B, T] ids at the per-row
+        device positions the caller has set on the blocks: no StepPlan -- nothing cached is forgotten, no id is sliced away --
+        and neither `last_forward_num_tokens` nor the blocks' start_pos move; the caller advances its positions by what it
+        accepts and restates the host bookkeeping (GraphedDecoder._sync_host_state)."""
+        if verify:
+            for b in self.blocks:
+                b.attn.verify_rows = True
+            try:
+                return self._run_blocks(input_ids)
+            finally:
+                for b in self.blocks:
+                    b.attn.verify_rows = False
         plan = StepPlan(input_ids, self.last_forward_num_tokens)
         input_ids, self.last_forward_num_tokens = plan.input_ids, plan.tokens_seen
         plan.apply(self.blocks)
+        return self._run_blocks(input_ids)
+
+    def _run_blocks(self, input_ids):
         h = self.embedding(input_ids)
         if self._stream_mode(h):
             x, ssq = None, None

@@ -1212,3 +1212,114 @@ def sample_tokens(logits, *, do_sample, temperature=1.0, top_k=0, top_p=1.0, see
             if bad:
                 raise _lib.AwqHipError(f"sample_tokens: rows {bad} hold NaN / +inf logits or keep no token (emitted pad)")
     return out
+
+
+# ---- speculative decoding: the verify step's attention (csrc/verify_attn.hip), acceptance and prompt-lookup drafts (csrc/spec.hip)
+
+_verify_workspaces = {}
+
+
+def verify_attention_splits(max_len, B, T, n_heads, n_kv_heads):
+    """split count of a verify_attention_rows launch sized for max_len (host only; the tests' error bound reads it)"""
+    rc = int(_lib.lib().awq_verify_attention_splits(int(max_len), int(B), int(T), int(n_heads), int(n_kv_heads)))
+    if rc < 1:
+        _lib.check(rc, "awq_verify_attention_splits")
+    return rc
+
+
+def verify_attention_rows(q, k_cache, v_cache, pos_rows, max_len=None, scale=None, k_scale=None, v_scale=None):
+    """q [B, T, Hq, 128] fp16 -- the q_out of rope_kv_append(pos_rows=..., S = T), which has already written cache rows
+    pos_rows[b] .. pos_rows[b] + T - 1 -- caches [>= B, Tmax, Hkv, 128] fp16, pos_rows int32 [B] on the device: the position of
+    sequence b's FIRST new token.  Returns [B, T, Hq, 128]: query (b, j) attends over cache rows t <= pos_rows[b] + j
+    (awq_verify_attention_rows).  T in 2 .. 8; max_len (default: the cache window) is the host bound of pos_rows[b] + T the
+    launch is sized for.  An fp8 cache is refused (NotImplementedError)."""
+    if k_scale is not None or v_scale is not None or k_cache.dtype == torch.uint8:
+        raise NotImplementedError('verify_attention_rows: kv_cache_dtype="fp8" is not supported by the speculative path')
+    _require_gpu(q, k_cache, v_cache, pos_rows)
+    if q.dtype != torch.float16 or k_cache.dtype != torch.float16 or v_cache.dtype != torch.float16 or q.dim() != 4:
+        raise _lib.AwqHipError("verify_attention_rows expects fp16 q [B, T, Hq, D] and fp16 caches")
+    B, T, Hq, D = q.shape
+    Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()) or k_cache.shape[0] < B or k_cache.shape != v_cache.shape:
+        raise _lib.AwqHipError("verify_attention_rows: caches must be contiguous [>=B, Tmax, Hkv, D]")
+    _check_rows("verify_attention_rows", "pos", pos_rows, None, B, q.device)
+    q = q.contiguous()
+    out = torch.empty_like(q)
+    L = _lib.lib()
+    key = (q.device.index if q.device.index is not None else torch.cuda.current_device(), _stream())
+    need = L.awq_verify_attention_workspace_bytes(B, T, Hq)
+    ws = _verify_workspaces.get(key)
+    if ws is None or ws.numel() < need:
+        if ws is not None:
+            _retired_raw.append(ws)  # a captured graph may still hold it
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
+        _verify_workspaces[key] = ws
+    if scale is None:
+        scale = D ** -0.5
+    with torch.cuda.device(q.device):
+        _lib.check(L.awq_verify_attention_rows(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos_rows),
+                                               int(max_len if max_len is not None else Tmax), B, T, Hq, Hkv, D, Tmax, float(scale),
+                                               _ptr(ws), ws.numel(), _stream()), "awq_verify_attention_rows")
+    return out
+
+
+def spec_params(eos_ids=(), pad=0, max_new_tokens=1, ngram_max=3):
+    """struct AwqSpecParams as a 48-byte CPU uint8 tensor the caller copies to the device"""
+    eos = [int(e) for e in eos_ids]
+    if len(eos) > 8:
+        raise ValueError("at most 8 EOS ids")
+    if int(ngram_max) < 1 or int(ngram_max) > 8:
+        raise ValueError(f"draft_ngram must be in 1 .. 8, got {ngram_max}")
+    p = _lib.AwqSpecParams()
+    p.n_eos, p.pad, p.max_new_tokens, p.ngram_max = len(eos), int(pad), int(max_new_tokens), int(ngram_max)
+    for i, e in enumerate(eos):
+        p.eos[i] = e
+    return torch.frombuffer(bytearray(bytes(p)), dtype=torch.uint8)
+
+
+def _spec_args(params, tok, hist, n_hist, pred=None, cnt=None, ring=None, finished=None, pos_rows=None, len_rows=None, status=None,
+               steps=None):
+    _require_gpu(params, tok, hist, n_hist, pred, cnt, ring, finished, pos_rows, len_rows, status, steps)
+    if tok.dtype != torch.int64 or tok.dim() != 2 or not tok.is_contiguous():
+        raise _lib.AwqHipError("spec: tok must be a contiguous int64 [B, T] tensor")
+    B, T = tok.shape
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] != B or not hist.is_contiguous():
+        raise _lib.AwqHipError("spec: hist must be a contiguous int32 [B, cap] tensor")
+    if params.numel() * params.element_size() < ctypes.sizeof(_lib.AwqSpecParams):
+        raise _lib.AwqHipError("spec: params must hold 48 bytes (spec_params)")
+    words = [("n_hist", n_hist), ("cnt", cnt), ("finished", finished), ("pos_rows", pos_rows), ("len_rows", len_rows),
+             ("steps", steps)]
+    for name, x in words:
+        if x is not None and (x.dtype != torch.int32 or x.numel() < B or not x.is_contiguous()):
+            raise _lib.AwqHipError(f"spec: {name} must be a contiguous int32 [B] tensor")
+    if ring is not None and (ring.dtype != torch.int32 or ring.dim() != 2 or ring.shape[0] != B or not ring.is_contiguous()):
+        raise _lib.AwqHipError("spec: ring must be a contiguous int32 [B, cap] tensor")
+    if pred is not None and (pred.dtype != torch.int64 or pred.numel() < B * T or not pred.is_contiguous()):
+        raise _lib.AwqHipError("spec: pred must be a contiguous int64 tensor of B * T elements")
+    if status is not None and (status.dtype != torch.int32 or status.numel() * 32 < B * T):
+        raise _lib.AwqHipError("spec: status must hold one bit per (row, slot)")
+    a = _lib.AwqSpecArgs()
+    a.struct_bytes, a.flags, a.B, a.T = ctypes.sizeof(_lib.AwqSpecArgs), 0, B, T
+    a.params, a.tok, a.pred = _ptr(params), _ptr(tok), _ptr(pred)
+    a.hist, a.hist_cap, a.n_hist, a.cnt = _ptr(hist), hist.shape[1], _ptr(n_hist), _ptr(cnt)
+    a.ring, a.ring_cap = _ptr(ring), ring.shape[1] if ring is not None else 0
+    a.finished, a.pos_rows, a.len_rows, a.status = _ptr(finished), _ptr(pos_rows), _ptr(len_rows), _ptr(status)
+    a.steps = _ptr(steps)
+    return a
+
+
+def spec_accept(params, tok, pred, hist, n_hist, cnt, ring, finished, pos_rows, len_rows, status=None, steps=None):
+    """awq_spec_accept on device words the caller owns (include/awq_hip.h states the rule; tests/spec_ref.py restates it).
+    Capturable, no sync."""
+    a = _spec_args(params, tok, hist, n_hist, pred, cnt, ring, finished, pos_rows, len_rows, status, steps)
+    with torch.cuda.device(tok.device):
+        a.stream = _stream()
+        _lib.check(_lib.lib().awq_spec_accept(ctypes.byref(a)), "awq_spec_accept")
+
+
+def ngram_draft(params, tok, hist, n_hist):
+    """awq_ngram_draft: tok [B, T] = each row's last token and its T - 1 prompt-lookup drafts.  Capturable, no sync."""
+    a = _spec_args(params, tok, hist, n_hist)
+    with torch.cuda.device(tok.device):
+        a.stream = _stream()
+        _lib.check(_lib.lib().awq_ngram_draft(ctypes.byref(a)), "awq_ngram_draft")

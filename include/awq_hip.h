@@ -649,6 +649,71 @@ AWQ_EXPORT int awq_sample_tokens_ex(const AwqSampleArgs* args, const AwqSamplePr
 AWQ_EXPORT int awq_sample_history_seed(uint32_t* history, int64_t history_stride, const int64_t* ids, int64_t ids_stride,
                                        int64_t B, int64_t S, int64_t V, void* stream);
 
+/* ---- speculative decoding: a k-token verify step (csrc/verify_attn.hip) and prompt-lookup drafts (csrc/spec.hip) ---------------
+ * awq_verify_attention_rows: attention of T = 2 .. 8 NEW tokens per sequence over the cache, at per-row device positions.
+ *   q [B, T, n_heads, 128] fp16 is the q_out of awq_rope_kv_append_rows(S = T), which has ALREADY written cache rows
+ *   pos_rows[b] .. pos_rows[b] + T - 1; out [B, T, n_heads, 128]: query (b, j) = softmax(scale q k^T) v over cache rows
+ *   t <= pos_rows[b] + j.  pos_rows [B] int32 on the device: the position of the FIRST new token of sequence b, clamped to the
+ *   cache as the append clamps the rows it writes (row = max(0, min(pos + j, max_seq - 1))).  max_len (T <= max_len <= max_seq)
+ *   is the host bound of pos_rows[b] + T the launch is sized for, as in awq_decode_attention_rows; rows are dealt to the splits on
+ *   the device.  head_dim 128, n_heads / n_kv_heads in {1, 2, 4, 8}, T in 2 .. 8 (AWQ_ERR_UNSUPPORTED otherwise); no soft cap, no
+ *   ALiBi, fp16 caches only.  workspace: awq_verify_attention_workspace_bytes(B, T, n_heads) bytes (needed when max_len > 256).
+ *   awq_verify_attention_splits: the split count of that launch with a large enough workspace (the tests' error bound reads it). */
+AWQ_EXPORT size_t awq_verify_attention_workspace_bytes(int64_t B, int64_t T, int64_t n_heads);
+AWQ_EXPORT int awq_verify_attention_splits(int64_t max_len, int64_t B, int64_t T, int64_t n_heads, int64_t n_kv_heads);
+AWQ_EXPORT int awq_verify_attention_rows(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
+                                         const int32_t* pos_rows, int64_t max_len, int64_t B, int64_t T, int64_t n_heads,
+                                         int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, void* workspace,
+                                         size_t workspace_bytes, void* stream);
+
+/* Acceptance and drafts: integer kernels, one block per sequence, capturable; every pointer is device memory.
+ * State per row b: hist [B, hist_cap] int32 (every token of the row by index: prompt, then generated), n_hist [B], cnt [B] (tokens
+ * generated so far), ring [B, ring_cap] (the generated tokens), finished [B], pos_rows / len_rows [B], the step's input
+ * tok [B, T] int64.  AwqSpecParams lives in DEVICE memory like AwqSampleParams.
+ * awq_spec_accept (row not finished; in = tok[b, :], pred [B * T] int64 = the greedy argmax of the step's logits at each slot):
+ *   a = the largest value in 0 .. T - 1 with in[j + 1] == pred[j] for all j < a; the new tokens are pred[0 .. a], cut after the
+ *   first EOS id among them (inclusive) and at max_new_tokens - cnt[b]; m >= 1 of them remain.  They are appended to ring[b, cnt ..]
+ *   and hist[b, n_hist ..] (writes past ring_cap / hist_cap are dropped); cnt, n_hist, pos_rows, len_rows += m; finished[b] = 1 if
+ *   an EOS was emitted or the budget is used up.  status (optional): the sampler's status words over the B * T slots -- a row with
+ *   a bit set in any of its T slots finishes without emitting (the sticky bit stays for the host).  A finished row emits nothing
+ *   and its words do not move.  steps (optional): steps[b] += 1 whenever row b emitted tokens -- the replays the row needed.
+ * awq_ngram_draft (h = hist[b, :n], n = n_hist[b] >= 1; a row with n = 0 is left alone): tok[b, 0] = h[n - 1].  For
+ *   g = ngram_max, ..., 1 with n > g: the largest s <= n - g - 1 with h[s : s + g] == h[n - g : n]; on the first g that matches,
+ *   tok[b, 1 + i] = h[s + g + i] while s + g + i < n; every slot left over, or all of them when no g matches, is h[n - 1].
+ *   ngram_max is clamped to 1 .. 8.  T in 2 .. 8 (AWQ_ERR_UNSUPPORTED otherwise). */
+typedef struct AwqSpecParams {
+    int32_t n_eos;          /* 0 .. 8 */
+    int32_t pad;            /* (unused by the kernels: the host pads finished rows) */
+    int32_t max_new_tokens;
+    int32_t ngram_max;
+    int32_t eos[8];
+} AwqSpecParams;
+
+typedef struct AwqSpecArgs {
+    uint32_t struct_bytes; /* sizeof(AwqSpecArgs) */
+    uint32_t flags;        /* 0 (reserved) */
+    int64_t B;
+    int64_t T;
+    const AwqSpecParams* params;
+    int64_t* tok;          /* [B, T] */
+    const int64_t* pred;   /* [B * T]; accept only */
+    int32_t* hist;         /* [B, hist_cap] */
+    int64_t hist_cap;
+    int32_t* n_hist;       /* [B] */
+    int32_t* cnt;          /* [B]; accept only, like every field below */
+    int32_t* ring;         /* [B, ring_cap] */
+    int64_t ring_cap;
+    int32_t* finished;     /* [B] */
+    int32_t* pos_rows;     /* [B] */
+    int32_t* len_rows;     /* [B] */
+    const uint32_t* status; /* [ceil(B * T / 32)] or NULL */
+    int32_t* steps;        /* [B] or NULL: += 1 for every call in which the row emitted tokens */
+    void* stream;
+} AwqSpecArgs;
+
+AWQ_EXPORT int awq_spec_accept(const AwqSpecArgs* args);
+AWQ_EXPORT int awq_ngram_draft(const AwqSpecArgs* args);
+
 #ifdef __cplusplus
 }
 #endif
