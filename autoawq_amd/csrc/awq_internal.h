@@ -161,16 +161,74 @@ int awq_launch_moe_route(const float* logits, float* topk_w, int* topk_ids, int*
 // decoder.hip: RMSNorm (+ residual add when `residual` is non-null), RoPE + KV-cache append, single-query attention
 int awq_launch_rmsnorm(const uint16_t* x, uint16_t* residual, const uint16_t* w, uint16_t* out, int64_t M, int64_t H,
                        float eps, hipStream_t st);
-int awq_launch_rope_kv_append(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, const float* cos_t,
-                              const float* sin_t, const int32_t* pos_dev, int start_pos, int B, int S, int Hq, int Hkv, int D,
-                              int rot, int Tmax, hipStream_t st, bool rows = false, float* k_scale = nullptr,
-                              float* v_scale = nullptr);
+// The arguments of the RoPE + append launch, as the C ABI passes them (the launcher narrows the sizes after capi.hip's range checks).
+struct AwqAppendArgs {
+    const uint16_t* qkv;  // [B, S, (Hq + 2 Hkv) D] fp16
+    uint16_t* q_out;      // [B, S, Hq, D]
+    void *k_cache, *v_cache;                      // [>= B, Tmax, Hkv, D]: fp16 rows, or e4m3 codes with
+    float *k_scale = nullptr, *v_scale = nullptr;  // their scales [>= B, Tmax, Hkv] (null: an fp16 cache)
+    const float *cos_t, *sin_t;
+    const int32_t* pos_dev = nullptr;  // device position word: one for the batch, or [B] with `rows`; null: start_pos
+    bool rows = false;
+    int64_t start_pos = 0, B, S, Hq, Hkv, D, rot, Tmax;
+    hipStream_t stream;
+};
+int awq_launch_rope_kv_append(const AwqAppendArgs& a);
+
+// The arguments of the decode-attention launch (and, with a token count, of the verify launch), as the C ABI passes them.
+struct AwqAttnArgs {
+    const uint16_t* q;  // query rows [B, Hq, D]; fused form: the raw qkv rows [B, (Hq + 2 Hkv) D]
+    const void *k_cache, *v_cache;                       // [>= B, Tmax, Hkv, D]: fp16 rows, or e4m3 codes with
+    const float *k_scale = nullptr, *v_scale = nullptr;  // their scales [>= B, Tmax, Hkv] (null: an fp16 cache).  The fused form
+                                                         // WRITES the new token's row of all four
+    uint16_t* out;                                 // [B, Hq, D]
+    const int32_t* len_dev = nullptr;  // device length word (fused form: the POSITION of the new token): one for the batch, or [B]
+    bool rows = false;                 // with `rows`; null: seq_len
+    int64_t seq_len = 0;               // host length (fused form: position), read where len_dev is null
+    int64_t max_len, B, Hq, Hkv, D, Tmax;  // max_len: the bound of the device word that the split is sized for
+    float scale, softcap = 0.f;
+    const float* alibi = nullptr;                     // slopes [Hq], or null
+    const float *cos_t = nullptr, *sin_t = nullptr;  // non-null: the fused form (rotate q / k, append k / v, attend)
+    void* workspace;
+    size_t workspace_bytes;
+    hipStream_t stream;
+};
 size_t awq_decode_attention_workspace_bytes_impl(int B, int Hq, int max_splits);
-int awq_launch_decode_attention(const uint16_t* q, uint16_t* k_cache, uint16_t* v_cache, uint16_t* out,
-                                const int32_t* len_dev, int seq_len, int max_len, int B, int Hq, int Hkv, int D, int Tmax,
-                                float scale, void* workspace, size_t workspace_bytes, const float* cos_t,
-                                const float* sin_t, hipStream_t st, float softcap = 0.f, const float* alibi_slopes = nullptr,
-                                bool rows = false, float* k_scale = nullptr, float* v_scale = nullptr);
+int awq_launch_decode_attention(const AwqAttnArgs& a);
+
+// Splits per KV head of the decode and verify launches: about 128 rows each (AWQ_ATTN_ROWS; A/B on the whole-model decode,
+// profiles/r04_attention_split_ab.txt: 128 rows 769 / 712 / 663 tok/s at 64 / 512 / 2048 tokens of context, 256 rows 772 / 657 /
+// 564, 64 rows 768 / 694 / 589), at most ~1024 blocks (AWQ_ATTN_BLOCKS) and 64 splits (the combine kernels' one-lane-per-split
+// step).  ONE split up to AWQ_ATTN_SINGLE = 256 rows: no partials, no combine launch at all -- what a short context pays for a
+// 32-way split sized for the whole cache was 9.5 + 5 us per layer (profiles/r03_whole_model_gemv_kernel_stats.txt); callers that
+// know the context on the host (modules/fused/decode.py: one hipGraph per length bucket) pass the bucket's bound as max_len.
+// (The constants are overridable in experiment builds: tools/attn_split_ab.py.)
+#ifndef AWQ_ATTN_BLOCKS
+#define AWQ_ATTN_BLOCKS 1024
+#endif
+#ifndef AWQ_ATTN_ROWS
+#define AWQ_ATTN_ROWS 128
+#endif
+#ifndef AWQ_ATTN_SINGLE
+#define AWQ_ATTN_SINGLE 256
+#endif
+// Host only.  len: the rows the launch is sized for; blocks_per_split: the blocks one split adds to the grid (decode: B Hkv,
+// verify: B Hkv token groups).  A workspace of workspace_bytes (0 where there is none) that holds fewer than the rule's splits
+// of bytes_per_split each limits the count to what fits; the defaults leave the rule alone.  blocks_per_split is 64-bit: the C ABI
+// admits B and Hkv up to 65535 each, and their product does not fit an int.
+static inline int awq_attn_splits(int len, int64_t blocks_per_split, size_t workspace_bytes = SIZE_MAX, size_t bytes_per_split = 1) {
+    int splits = len <= AWQ_ATTN_SINGLE ? 1 : (len + AWQ_ATTN_ROWS - 1) / AWQ_ATTN_ROWS;
+    const int by_blocks = AWQ_ATTN_BLOCKS / blocks_per_split > 1 ? (int)(AWQ_ATTN_BLOCKS / blocks_per_split) : 1;
+    if (splits > by_blocks) splits = by_blocks;
+    if (splits < 1) splits = 1;
+    if (splits > 64) splits = 64;
+    if (splits > 1 && workspace_bytes / bytes_per_split < (size_t)splits) {
+        splits = (int)(workspace_bytes / bytes_per_split);
+        if (splits < 1) splits = 1;
+    }
+    return splits;
+}
+
 // fp8 KV cache (k_scale / v_scale above non-NULL: the caches hold e4m3 codes): fp16 rows <-> codes + scales
 int awq_launch_kv_quant_fp8(const uint16_t* x, uint8_t* codes, float* scales, int B, int S, int Hkv, int Tmax, int start,
                             hipStream_t st);
@@ -180,6 +238,5 @@ int awq_launch_kv_dequant_fp8(const uint8_t* codes, const float* scales, uint16_
 // verify_attn.hip: attention of T = 2 .. 8 new tokens per sequence over the cache at per-row device positions (speculative decoding)
 int awq_verify_attention_splits_impl(int max_len, int B, int T, int Hq, int Hkv);
 size_t awq_verify_attention_workspace_bytes_impl(int B, int T, int Hq, int splits);
-int awq_launch_verify_attention(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
-                                const int32_t* pos_rows, int max_len, int B, int T, int Hq, int Hkv, int D, int Tmax, float scale,
-                                void* workspace, size_t workspace_bytes, hipStream_t st);
+// (a: an fp16 cache, the per-row word and max_len; seq_len, softcap, alibi and the tables are not read)
+int awq_launch_verify_attention(const AwqAttnArgs& a, int T);

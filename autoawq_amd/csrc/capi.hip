@@ -642,27 +642,96 @@ int awq_rmsnorm_forward(const uint16_t* x, uint16_t* residual, const uint16_t* w
     return awq_launch_rmsnorm(x, residual, weight, out, M, H, eps, static_cast<hipStream_t>(stream));
 }
 
+// ---- RoPE + append and decode attention (decoder.hip): an entry point fills the launch's arguments; one function per family
+// checks them and launches.  The entry points of a family differ in what they require; the one place where they also differ in
+// the order of two checks is noted at decode_attention below.
+
+// fp8 KV cache (KV8): the caches, their scale arrays and head_dim == 128
+static int kv8_check(const void* kc, const void* vc, const float* ks, const float* vs, int64_t head_dim) {
+    if (!kc || !vc || !ks || !vs) return AWQ_ERR_NULL;
+    if (head_dim != 128) return AWQ_ERR_UNSUPPORTED;
+    if (!aligned16(kc) || !aligned16(vc) || (reinterpret_cast<uintptr_t>(ks) & 3) || (reinterpret_cast<uintptr_t>(vs) & 3))
+        return AWQ_ERR_BAD_ALIGNMENT;
+    return AWQ_OK;
+}
+
+// kv8: an *_fp8 entry (the scale arrays are required, and the caches are checked with them)
+static int rope_kv_append(const AwqAppendArgs& a, bool kv8) {
+    if (a.B < 0 || a.S < 0 || a.B * a.S > INT32_MAX / 1024 || a.Tmax < 1 || a.Tmax > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (a.B * a.S == 0) return AWQ_OK;
+    if (!a.qkv || !a.q_out || (a.rows && !a.pos_dev) || (a.rot > 0 && (!a.cos_t || !a.sin_t))) return AWQ_ERR_NULL;
+    if (kv8) {
+        if (int rc = kv8_check(a.k_cache, a.v_cache, a.k_scale, a.v_scale, a.D)) return rc;
+    } else if (!a.k_cache || !a.v_cache) {
+        return AWQ_ERR_NULL;
+    }
+    return awq_launch_rope_kv_append(a);
+}
+
+// kv8: as above.  rope: a fused entry -- the tables are required, and without a device word the host position (a.seq_len) must lie
+// inside the cache.  The soft cap is checked for every entry: the ones that take none leave it 0.  An fp8 entry refuses a head
+// size (kv8_check) BEFORE it looks at the alignment of q and out, an fp16 entry after (the launcher): kept as published.
+static int decode_attention(const AwqAttnArgs& a, bool kv8, bool rope) {
+    if (a.B < 0 || a.B > 65535 || a.Hq < 1 || a.Hkv < 1 || a.Hkv > 65535 || a.Tmax > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (!(a.softcap >= 0.f)) return AWQ_ERR_BAD_SHAPE;
+    if (a.B == 0) return AWQ_OK;
+    if (!a.q || !a.out || (a.rows && !a.len_dev) || (rope && (!a.cos_t || !a.sin_t))) return AWQ_ERR_NULL;
+    if (kv8) {
+        if (int rc = kv8_check(a.k_cache, a.v_cache, a.k_scale, a.v_scale, a.D)) return rc;
+    } else {
+        if (!a.k_cache || !a.v_cache) return AWQ_ERR_NULL;
+        if (!aligned16(a.k_cache) || !aligned16(a.v_cache)) return AWQ_ERR_BAD_ALIGNMENT;
+    }
+    if (!aligned16(a.q) || !aligned16(a.out)) return AWQ_ERR_BAD_ALIGNMENT;
+    if (rope && !a.len_dev && (a.seq_len < 0 || a.seq_len >= a.Tmax)) return AWQ_ERR_BAD_SHAPE;
+    return awq_launch_decode_attention(a);
+}
+
 int awq_rope_kv_append(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, const float* cos_table,
                        const float* sin_table, const int32_t* pos_dev, int64_t start_pos, int64_t B, int64_t S,
                        int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim, int64_t max_seq,
                        void* stream) {
-    if (B < 0 || S < 0 || B * S > INT32_MAX / 1024 || max_seq < 1 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (B * S == 0) return AWQ_OK;
-    if (!qkv || !q_out || !k_cache || !v_cache || (rotary_dim > 0 && (!cos_table || !sin_table))) return AWQ_ERR_NULL;
-    return awq_launch_rope_kv_append(qkv, q_out, k_cache, v_cache, cos_table, sin_table, pos_dev, (int)start_pos, (int)B,
-                                     (int)S, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)rotary_dim, (int)max_seq,
-                                     static_cast<hipStream_t>(stream));
+    AwqAppendArgs a;
+    a.qkv = qkv, a.q_out = q_out, a.k_cache = k_cache, a.v_cache = v_cache, a.cos_t = cos_table, a.sin_t = sin_table;
+    a.pos_dev = pos_dev, a.start_pos = start_pos;
+    a.B = B, a.S = S, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.rot = rotary_dim, a.Tmax = max_seq;
+    a.stream = static_cast<hipStream_t>(stream);
+    return rope_kv_append(a, false);
 }
 
 int awq_rope_kv_append_rows(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, const float* cos_table,
                             const float* sin_table, const int32_t* pos_rows, int64_t B, int64_t S, int64_t n_heads,
                             int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim, int64_t max_seq, void* stream) {
-    if (B < 0 || S < 0 || B * S > INT32_MAX / 1024 || max_seq < 1 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (B * S == 0) return AWQ_OK;
-    if (!qkv || !q_out || !k_cache || !v_cache || !pos_rows || (rotary_dim > 0 && (!cos_table || !sin_table))) return AWQ_ERR_NULL;
-    return awq_launch_rope_kv_append(qkv, q_out, k_cache, v_cache, cos_table, sin_table, pos_rows, 0, (int)B, (int)S,
-                                     (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)rotary_dim, (int)max_seq,
-                                     static_cast<hipStream_t>(stream), true);
+    AwqAppendArgs a;
+    a.qkv = qkv, a.q_out = q_out, a.k_cache = k_cache, a.v_cache = v_cache, a.cos_t = cos_table, a.sin_t = sin_table;
+    a.pos_dev = pos_rows, a.rows = true;
+    a.B = B, a.S = S, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.rot = rotary_dim, a.Tmax = max_seq;
+    a.stream = static_cast<hipStream_t>(stream);
+    return rope_kv_append(a, false);
+}
+
+int awq_rope_kv_append_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k_cache, uint8_t* v_cache, float* k_scale, float* v_scale,
+                           const float* cos_table, const float* sin_table, const int32_t* pos_dev, int64_t start_pos, int64_t B,
+                           int64_t S, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim, int64_t max_seq,
+                           void* stream) {
+    AwqAppendArgs a;
+    a.qkv = qkv, a.q_out = q_out, a.k_cache = k_cache, a.v_cache = v_cache, a.k_scale = k_scale, a.v_scale = v_scale;
+    a.cos_t = cos_table, a.sin_t = sin_table, a.pos_dev = pos_dev, a.start_pos = start_pos;
+    a.B = B, a.S = S, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.rot = rotary_dim, a.Tmax = max_seq;
+    a.stream = static_cast<hipStream_t>(stream);
+    return rope_kv_append(a, true);
+}
+
+int awq_rope_kv_append_rows_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k_cache, uint8_t* v_cache, float* k_scale,
+                                float* v_scale, const float* cos_table, const float* sin_table, const int32_t* pos_rows, int64_t B,
+                                int64_t S, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim,
+                                int64_t max_seq, void* stream) {
+    AwqAppendArgs a;
+    a.qkv = qkv, a.q_out = q_out, a.k_cache = k_cache, a.v_cache = v_cache, a.k_scale = k_scale, a.v_scale = v_scale;
+    a.cos_t = cos_table, a.sin_t = sin_table, a.pos_dev = pos_rows, a.rows = true;
+    a.B = B, a.S = S, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.rot = rotary_dim, a.Tmax = max_seq;
+    a.stream = static_cast<hipStream_t>(stream);
+    return rope_kv_append(a, true);
 }
 
 size_t awq_decode_attention_workspace_bytes(int64_t B, int64_t n_heads) {
@@ -670,75 +739,121 @@ size_t awq_decode_attention_workspace_bytes(int64_t B, int64_t n_heads) {
     return awq_decode_attention_workspace_bytes_impl((int)B, (int)n_heads, 64);
 }
 
-int awq_decode_attention(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
-                         const int32_t* len_dev, int64_t seq_len, int64_t max_len, int64_t B, int64_t n_heads,
-                         int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, void* workspace,
-                         size_t workspace_bytes, void* stream) {
-    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (B == 0) return AWQ_OK;
-    if (!q || !k_cache || !v_cache || !out) return AWQ_ERR_NULL;
-    if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    return awq_launch_decode_attention(q, const_cast<uint16_t*>(k_cache), const_cast<uint16_t*>(v_cache), out, len_dev,
-                                       (int)seq_len, (int)max_len, (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim,
-                                       (int)max_seq, scale, workspace, workspace_bytes, nullptr, nullptr,
-                                       static_cast<hipStream_t>(stream));
-}
-
 int awq_decode_attention_ex(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
                             const int32_t* len_dev, int64_t seq_len, int64_t max_len, int64_t B, int64_t n_heads,
                             int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, float softcap,
                             const float* alibi_slopes, void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (!(softcap >= 0.f)) return AWQ_ERR_BAD_SHAPE;
-    if (B == 0) return AWQ_OK;
-    if (!q || !k_cache || !v_cache || !out) return AWQ_ERR_NULL;
-    if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    return awq_launch_decode_attention(q, const_cast<uint16_t*>(k_cache), const_cast<uint16_t*>(v_cache), out, len_dev,
-                                       (int)seq_len, (int)max_len, (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim,
-                                       (int)max_seq, scale, workspace, workspace_bytes, nullptr, nullptr,
-                                       static_cast<hipStream_t>(stream), softcap, alibi_slopes);
+    AwqAttnArgs a;
+    a.q = q, a.k_cache = k_cache, a.v_cache = v_cache, a.out = out, a.len_dev = len_dev, a.seq_len = seq_len, a.max_len = max_len;
+    a.B = B, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.Tmax = max_seq;
+    a.scale = scale, a.softcap = softcap, a.alibi = alibi_slopes;
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes, a.stream = static_cast<hipStream_t>(stream);
+    return decode_attention(a, false, false);
+}
+
+int awq_decode_attention(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
+                         const int32_t* len_dev, int64_t seq_len, int64_t max_len, int64_t B, int64_t n_heads,
+                         int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    return awq_decode_attention_ex(q, k_cache, v_cache, out, len_dev, seq_len, max_len, B, n_heads, n_kv_heads, head_dim, max_seq,
+                                   scale, 0.f, nullptr, workspace, workspace_bytes, stream);
 }
 
 int awq_decode_attention_rope(const uint16_t* qkv, uint16_t* k_cache, uint16_t* v_cache, const float* cos_table,
                               const float* sin_table, uint16_t* out, const int32_t* pos_dev, int64_t start_pos,
                               int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim,
                               int64_t max_seq, float scale, void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (B == 0) return AWQ_OK;
-    if (!qkv || !k_cache || !v_cache || !out || !cos_table || !sin_table) return AWQ_ERR_NULL;
-    if (!aligned16(qkv) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    if (!pos_dev && (start_pos < 0 || start_pos >= max_seq)) return AWQ_ERR_BAD_SHAPE;
-    return awq_launch_decode_attention(qkv, k_cache, v_cache, out, pos_dev, (int)start_pos, (int)max_len, (int)B, (int)n_heads,
-                                       (int)n_kv_heads, (int)head_dim, (int)max_seq, scale, workspace, workspace_bytes,
-                                       cos_table, sin_table, static_cast<hipStream_t>(stream));
+    AwqAttnArgs a;
+    a.q = qkv, a.k_cache = k_cache, a.v_cache = v_cache, a.out = out, a.len_dev = pos_dev, a.seq_len = start_pos, a.max_len = max_len;
+    a.B = B, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.Tmax = max_seq;
+    a.scale = scale, a.cos_t = cos_table, a.sin_t = sin_table;
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes, a.stream = static_cast<hipStream_t>(stream);
+    return decode_attention(a, false, true);
 }
 
 int awq_decode_attention_rows(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
                               const int32_t* len_rows, int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads,
                               int64_t head_dim, int64_t max_seq, float scale, float softcap, const float* alibi_slopes,
                               void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (!(softcap >= 0.f)) return AWQ_ERR_BAD_SHAPE;
-    if (B == 0) return AWQ_OK;
-    if (!q || !k_cache || !v_cache || !out || !len_rows) return AWQ_ERR_NULL;
-    if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    return awq_launch_decode_attention(q, const_cast<uint16_t*>(k_cache), const_cast<uint16_t*>(v_cache), out, len_rows, 1,
-                                       (int)max_len, (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_seq, scale,
-                                       workspace, workspace_bytes, nullptr, nullptr, static_cast<hipStream_t>(stream), softcap,
-                                       alibi_slopes, true);
+    AwqAttnArgs a;
+    a.q = q, a.k_cache = k_cache, a.v_cache = v_cache, a.out = out, a.len_dev = len_rows, a.rows = true, a.seq_len = 1, a.max_len = max_len;
+    a.B = B, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.Tmax = max_seq;
+    a.scale = scale, a.softcap = softcap, a.alibi = alibi_slopes;
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes, a.stream = static_cast<hipStream_t>(stream);
+    return decode_attention(a, false, false);
 }
 
 int awq_decode_attention_rope_rows(const uint16_t* qkv, uint16_t* k_cache, uint16_t* v_cache, const float* cos_table,
                                    const float* sin_table, uint16_t* out, const int32_t* pos_rows, int64_t max_len, int64_t B,
                                    int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (B == 0) return AWQ_OK;
-    if (!qkv || !k_cache || !v_cache || !out || !cos_table || !sin_table || !pos_rows) return AWQ_ERR_NULL;
-    if (!aligned16(qkv) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    return awq_launch_decode_attention(qkv, k_cache, v_cache, out, pos_rows, 0, (int)max_len, (int)B, (int)n_heads,
-                                       (int)n_kv_heads, (int)head_dim, (int)max_seq, scale, workspace, workspace_bytes,
-                                       cos_table, sin_table, static_cast<hipStream_t>(stream), 0.f, nullptr, true);
+    AwqAttnArgs a;
+    a.q = qkv, a.k_cache = k_cache, a.v_cache = v_cache, a.out = out, a.len_dev = pos_rows, a.rows = true, a.max_len = max_len;
+    a.B = B, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.Tmax = max_seq;
+    a.scale = scale, a.cos_t = cos_table, a.sin_t = sin_table;
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes, a.stream = static_cast<hipStream_t>(stream);
+    return decode_attention(a, false, true);
+}
+
+int awq_decode_attention_ex_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache, const float* k_scale,
+                                const float* v_scale, uint16_t* out, const int32_t* len_dev, int64_t seq_len, int64_t max_len,
+                                int64_t B, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale,
+                                float softcap, const float* alibi_slopes, void* workspace, size_t workspace_bytes, void* stream) {
+    AwqAttnArgs a;
+    a.q = q, a.k_cache = k_cache, a.v_cache = v_cache, a.k_scale = k_scale, a.v_scale = v_scale, a.out = out;
+    a.len_dev = len_dev, a.seq_len = seq_len, a.max_len = max_len;
+    a.B = B, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.Tmax = max_seq;
+    a.scale = scale, a.softcap = softcap, a.alibi = alibi_slopes;
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes, a.stream = static_cast<hipStream_t>(stream);
+    return decode_attention(a, true, false);
+}
+
+int awq_decode_attention_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache, const float* k_scale,
+                             const float* v_scale, uint16_t* out, const int32_t* len_dev, int64_t seq_len, int64_t max_len, int64_t B,
+                             int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    return awq_decode_attention_ex_fp8(q, k_cache, v_cache, k_scale, v_scale, out, len_dev, seq_len, max_len, B, n_heads,
+                                       n_kv_heads, head_dim, max_seq, scale, 0.f, nullptr, workspace, workspace_bytes, stream);
+}
+
+int awq_decode_attention_rope_fp8(const uint16_t* qkv, uint8_t* k_cache, uint8_t* v_cache, float* k_scale, float* v_scale,
+                                  const float* cos_table, const float* sin_table, uint16_t* out, const int32_t* pos_dev,
+                                  int64_t start_pos, int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads,
+                                  int64_t head_dim, int64_t max_seq, float scale, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+    AwqAttnArgs a;
+    a.q = qkv, a.k_cache = k_cache, a.v_cache = v_cache, a.k_scale = k_scale, a.v_scale = v_scale, a.out = out;
+    a.len_dev = pos_dev, a.seq_len = start_pos, a.max_len = max_len;
+    a.B = B, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.Tmax = max_seq;
+    a.scale = scale, a.cos_t = cos_table, a.sin_t = sin_table;
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes, a.stream = static_cast<hipStream_t>(stream);
+    return decode_attention(a, true, true);
+}
+
+int awq_decode_attention_rows_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache, const float* k_scale,
+                                  const float* v_scale, uint16_t* out, const int32_t* len_rows, int64_t max_len, int64_t B,
+                                  int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, float softcap,
+                                  const float* alibi_slopes, void* workspace, size_t workspace_bytes, void* stream) {
+    AwqAttnArgs a;
+    a.q = q, a.k_cache = k_cache, a.v_cache = v_cache, a.k_scale = k_scale, a.v_scale = v_scale, a.out = out;
+    a.len_dev = len_rows, a.rows = true, a.seq_len = 1, a.max_len = max_len;
+    a.B = B, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.Tmax = max_seq;
+    a.scale = scale, a.softcap = softcap, a.alibi = alibi_slopes;
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes, a.stream = static_cast<hipStream_t>(stream);
+    return decode_attention(a, true, false);
+}
+
+int awq_decode_attention_rope_rows_fp8(const uint16_t* qkv, uint8_t* k_cache, uint8_t* v_cache, float* k_scale, float* v_scale,
+                                       const float* cos_table, const float* sin_table, uint16_t* out, const int32_t* pos_rows,
+                                       int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim,
+                                       int64_t max_seq, float scale, void* workspace, size_t workspace_bytes, void* stream) {
+    AwqAttnArgs a;
+    a.q = qkv, a.k_cache = k_cache, a.v_cache = v_cache, a.k_scale = k_scale, a.v_scale = v_scale, a.out = out;
+    a.len_dev = pos_rows, a.rows = true, a.max_len = max_len;
+    a.B = B, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.Tmax = max_seq;
+    a.scale = scale, a.cos_t = cos_table, a.sin_t = sin_table;
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes, a.stream = static_cast<hipStream_t>(stream);
+    return decode_attention(a, true, true);
 }
 
 // ---- speculative decoding (verify_attn.hip): T new tokens per sequence at per-row device positions
@@ -765,121 +880,14 @@ int awq_verify_attention_rows(const uint16_t* q, const uint16_t* k_cache, const 
     if (B == 0) return AWQ_OK;
     if (!q || !k_cache || !v_cache || !out || !pos_rows) return AWQ_ERR_NULL;
     if (!aligned16(q) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    return awq_launch_verify_attention(q, k_cache, v_cache, out, pos_rows, (int)max_len, (int)B, (int)T, (int)n_heads,
-                                       (int)n_kv_heads, (int)head_dim, (int)max_seq, scale, workspace, workspace_bytes,
-                                       static_cast<hipStream_t>(stream));
+    AwqAttnArgs a;
+    a.q = q, a.k_cache = k_cache, a.v_cache = v_cache, a.out = out, a.len_dev = pos_rows, a.rows = true, a.max_len = max_len;
+    a.B = B, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.Tmax = max_seq, a.scale = scale;
+    a.workspace = workspace, a.workspace_bytes = workspace_bytes, a.stream = static_cast<hipStream_t>(stream);
+    return awq_launch_verify_attention(a, (int)T);
 }
 
-// ---- fp8 KV cache (decoder.hip, KV8): same checks as the fp16 entry points, plus head_dim == 128 and the scale arrays
-static int kv8_check(const void* kc, const void* vc, const float* ks, const float* vs, int64_t head_dim) {
-    if (!kc || !vc || !ks || !vs) return AWQ_ERR_NULL;
-    if (head_dim != 128) return AWQ_ERR_UNSUPPORTED;
-    if (!aligned16(kc) || !aligned16(vc) || (reinterpret_cast<uintptr_t>(ks) & 3) || (reinterpret_cast<uintptr_t>(vs) & 3))
-        return AWQ_ERR_BAD_ALIGNMENT;
-    return AWQ_OK;
-}
-
-int awq_rope_kv_append_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k_cache, uint8_t* v_cache, float* k_scale, float* v_scale,
-                           const float* cos_table, const float* sin_table, const int32_t* pos_dev, int64_t start_pos, int64_t B,
-                           int64_t S, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim, int64_t max_seq,
-                           void* stream) {
-    if (B < 0 || S < 0 || B * S > INT32_MAX / 1024 || max_seq < 1 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (B * S == 0) return AWQ_OK;
-    if (!qkv || !q_out || (rotary_dim > 0 && (!cos_table || !sin_table))) return AWQ_ERR_NULL;
-    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
-    return awq_launch_rope_kv_append(qkv, q_out, reinterpret_cast<uint16_t*>(k_cache), reinterpret_cast<uint16_t*>(v_cache),
-                                     cos_table, sin_table, pos_dev, (int)start_pos, (int)B, (int)S, (int)n_heads, (int)n_kv_heads,
-                                     (int)head_dim, (int)rotary_dim, (int)max_seq, static_cast<hipStream_t>(stream), false, k_scale,
-                                     v_scale);
-}
-
-int awq_rope_kv_append_rows_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k_cache, uint8_t* v_cache, float* k_scale,
-                                float* v_scale, const float* cos_table, const float* sin_table, const int32_t* pos_rows, int64_t B,
-                                int64_t S, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim,
-                                int64_t max_seq, void* stream) {
-    if (B < 0 || S < 0 || B * S > INT32_MAX / 1024 || max_seq < 1 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (B * S == 0) return AWQ_OK;
-    if (!qkv || !q_out || !pos_rows || (rotary_dim > 0 && (!cos_table || !sin_table))) return AWQ_ERR_NULL;
-    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
-    return awq_launch_rope_kv_append(qkv, q_out, reinterpret_cast<uint16_t*>(k_cache), reinterpret_cast<uint16_t*>(v_cache),
-                                     cos_table, sin_table, pos_rows, 0, (int)B, (int)S, (int)n_heads, (int)n_kv_heads, (int)head_dim,
-                                     (int)rotary_dim, (int)max_seq, static_cast<hipStream_t>(stream), true, k_scale, v_scale);
-}
-
-int awq_decode_attention_ex_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache, const float* k_scale,
-                                const float* v_scale, uint16_t* out, const int32_t* len_dev, int64_t seq_len, int64_t max_len,
-                                int64_t B, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale,
-                                float softcap, const float* alibi_slopes, void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (!(softcap >= 0.f)) return AWQ_ERR_BAD_SHAPE;
-    if (B == 0) return AWQ_OK;
-    if (!q || !out) return AWQ_ERR_NULL;
-    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
-    if (!aligned16(q) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    return awq_launch_decode_attention(q, reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(k_cache)),
-                                       reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(v_cache)), out, len_dev, (int)seq_len,
-                                       (int)max_len, (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_seq, scale,
-                                       workspace, workspace_bytes, nullptr, nullptr, static_cast<hipStream_t>(stream), softcap,
-                                       alibi_slopes, false, const_cast<float*>(k_scale), const_cast<float*>(v_scale));
-}
-
-int awq_decode_attention_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache, const float* k_scale,
-                             const float* v_scale, uint16_t* out, const int32_t* len_dev, int64_t seq_len, int64_t max_len, int64_t B,
-                             int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, void* workspace,
-                             size_t workspace_bytes, void* stream) {
-    return awq_decode_attention_ex_fp8(q, k_cache, v_cache, k_scale, v_scale, out, len_dev, seq_len, max_len, B, n_heads,
-                                       n_kv_heads, head_dim, max_seq, scale, 0.f, nullptr, workspace, workspace_bytes, stream);
-}
-
-int awq_decode_attention_rope_fp8(const uint16_t* qkv, uint8_t* k_cache, uint8_t* v_cache, float* k_scale, float* v_scale,
-                                  const float* cos_table, const float* sin_table, uint16_t* out, const int32_t* pos_dev,
-                                  int64_t start_pos, int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads,
-                                  int64_t head_dim, int64_t max_seq, float scale, void* workspace, size_t workspace_bytes,
-                                  void* stream) {
-    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (B == 0) return AWQ_OK;
-    if (!qkv || !out || !cos_table || !sin_table) return AWQ_ERR_NULL;
-    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
-    if (!aligned16(qkv) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    if (!pos_dev && (start_pos < 0 || start_pos >= max_seq)) return AWQ_ERR_BAD_SHAPE;
-    return awq_launch_decode_attention(qkv, reinterpret_cast<uint16_t*>(k_cache), reinterpret_cast<uint16_t*>(v_cache), out, pos_dev,
-                                       (int)start_pos, (int)max_len, (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim,
-                                       (int)max_seq, scale, workspace, workspace_bytes, cos_table, sin_table,
-                                       static_cast<hipStream_t>(stream), 0.f, nullptr, false, k_scale, v_scale);
-}
-
-int awq_decode_attention_rows_fp8(const uint16_t* q, const uint8_t* k_cache, const uint8_t* v_cache, const float* k_scale,
-                                  const float* v_scale, uint16_t* out, const int32_t* len_rows, int64_t max_len, int64_t B,
-                                  int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale, float softcap,
-                                  const float* alibi_slopes, void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (!(softcap >= 0.f)) return AWQ_ERR_BAD_SHAPE;
-    if (B == 0) return AWQ_OK;
-    if (!q || !out || !len_rows) return AWQ_ERR_NULL;
-    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
-    if (!aligned16(q) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    return awq_launch_decode_attention(q, reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(k_cache)),
-                                       reinterpret_cast<uint16_t*>(const_cast<uint8_t*>(v_cache)), out, len_rows, 1, (int)max_len,
-                                       (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_seq, scale, workspace,
-                                       workspace_bytes, nullptr, nullptr, static_cast<hipStream_t>(stream), softcap, alibi_slopes,
-                                       true, const_cast<float*>(k_scale), const_cast<float*>(v_scale));
-}
-
-int awq_decode_attention_rope_rows_fp8(const uint16_t* qkv, uint8_t* k_cache, uint8_t* v_cache, float* k_scale, float* v_scale,
-                                       const float* cos_table, const float* sin_table, uint16_t* out, const int32_t* pos_rows,
-                                       int64_t max_len, int64_t B, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim,
-                                       int64_t max_seq, float scale, void* workspace, size_t workspace_bytes, void* stream) {
-    if (B < 0 || B > 65535 || n_heads < 1 || n_kv_heads < 1 || n_kv_heads > 65535 || max_seq > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (B == 0) return AWQ_OK;
-    if (!qkv || !out || !cos_table || !sin_table || !pos_rows) return AWQ_ERR_NULL;
-    if (int rc = kv8_check(k_cache, v_cache, k_scale, v_scale, head_dim)) return rc;
-    if (!aligned16(qkv) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    return awq_launch_decode_attention(qkv, reinterpret_cast<uint16_t*>(k_cache), reinterpret_cast<uint16_t*>(v_cache), out, pos_rows, 0,
-                                       (int)max_len, (int)B, (int)n_heads, (int)n_kv_heads, (int)head_dim, (int)max_seq, scale,
-                                       workspace, workspace_bytes, cos_table, sin_table, static_cast<hipStream_t>(stream), 0.f, nullptr,
-                                       true, k_scale, v_scale);
-}
-
+// ---- fp8 KV cache (decoder.hip, KV8): fp16 rows <-> codes + scales
 int awq_kv_quant_fp8(const uint16_t* x, uint8_t* cache, float* scales, int64_t B, int64_t S, int64_t n_kv_heads, int64_t head_dim,
                      int64_t max_seq, int64_t start_pos, void* stream) {
     if (B < 0 || S < 0 || n_kv_heads < 1 || max_seq < 1 || max_seq > INT32_MAX || start_pos < 0 || start_pos + S > max_seq ||

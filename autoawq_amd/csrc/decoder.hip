@@ -615,28 +615,28 @@ int awq_launch_rmsnorm(const uint16_t* x, uint16_t* residual, const uint16_t* w,
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
 
-int awq_launch_rope_kv_append(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, const float* cos_t,
-                              const float* sin_t, const int32_t* pos_dev, int start_pos, int B, int S, int Hq, int Hkv, int D,
-                              int rot, int Tmax, hipStream_t st, bool rows, float* k_scale, float* v_scale) {
+int awq_launch_rope_kv_append(const AwqAppendArgs& a) {
+    const int start_pos = (int)a.start_pos, B = (int)a.B, S = (int)a.S, Hq = (int)a.Hq, Hkv = (int)a.Hkv, D = (int)a.D, rot = (int)a.rot,
+              Tmax = (int)a.Tmax;
     if (B < 0 || S < 0 || Hq < 1 || Hkv < 1 || D < 2 || D % 2 || D > 256 || rot < 0 || rot > D || rot % 2)
         return AWQ_ERR_BAD_SHAPE;
-    if (rows && !pos_dev) return AWQ_ERR_NULL;
-    if (!pos_dev && (start_pos < 0 || start_pos + S > Tmax)) return AWQ_ERR_BAD_SHAPE;
-    const bool kv8 = k_scale != nullptr;
-    if (kv8 && (!v_scale)) return AWQ_ERR_NULL;
+    if (a.rows && !a.pos_dev) return AWQ_ERR_NULL;
+    if (!a.pos_dev && (start_pos < 0 || start_pos + S > Tmax)) return AWQ_ERR_BAD_SHAPE;
+    const bool kv8 = a.k_scale != nullptr;
+    if (kv8 && !a.v_scale) return AWQ_ERR_NULL;
     if (kv8 && D != 128) return AWQ_ERR_UNSUPPORTED;
     if (B * S == 0) return AWQ_OK;
     const unsigned blocks = (unsigned)((int64_t)B * S * (Hq + 2 * Hkv));
-    if (kv8) {
-        hipLaunchKernelGGL(rows ? awq_rope_kv_append_fp8_kernel<true> : awq_rope_kv_append_fp8_kernel<false>, dim3(blocks), dim3(64), 0,
-                           st, reinterpret_cast<const half_t*>(qkv), reinterpret_cast<half_t*>(q_out),
-                           reinterpret_cast<uint8_t*>(k_cache), reinterpret_cast<uint8_t*>(v_cache), k_scale, v_scale, cos_t, sin_t,
-                           pos_dev, start_pos, S, Hq, Hkv, rot, Tmax);
-        return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(rows ? awq_rope_kv_append_kernel<true> : awq_rope_kv_append_kernel<false>, dim3(blocks), dim3(D / 2), 0, st,
-                       reinterpret_cast<const half_t*>(qkv), reinterpret_cast<half_t*>(q_out), reinterpret_cast<half_t*>(k_cache),
-                       reinterpret_cast<half_t*>(v_cache), cos_t, sin_t, pos_dev, start_pos, S, Hq, Hkv, D, rot, Tmax);
+    const half_t* qkv = reinterpret_cast<const half_t*>(a.qkv);
+    half_t* q_out = reinterpret_cast<half_t*>(a.q_out);
+    if (kv8)
+        hipLaunchKernelGGL(a.rows ? awq_rope_kv_append_fp8_kernel<true> : awq_rope_kv_append_fp8_kernel<false>, dim3(blocks), dim3(64),
+                           0, a.stream, qkv, q_out, static_cast<uint8_t*>(a.k_cache), static_cast<uint8_t*>(a.v_cache), a.k_scale,
+                           a.v_scale, a.cos_t, a.sin_t, a.pos_dev, start_pos, S, Hq, Hkv, rot, Tmax);
+    else
+        hipLaunchKernelGGL(a.rows ? awq_rope_kv_append_kernel<true> : awq_rope_kv_append_kernel<false>, dim3(blocks), dim3(D / 2), 0,
+                           a.stream, qkv, q_out, static_cast<half_t*>(a.k_cache), static_cast<half_t*>(a.v_cache), a.cos_t, a.sin_t,
+                           a.pos_dev, start_pos, S, Hq, Hkv, D, rot, Tmax);
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
 
@@ -644,101 +644,73 @@ size_t awq_decode_attention_workspace_bytes_impl(int B, int Hq, int max_splits) 
     return (size_t)B * Hq * max_splits * (128 + 2) * sizeof(float);
 }
 
-// ksc != nullptr: the fp8 kernel (codes in kc / vc, scales in ksc / vsc)
-template <int G, bool FUSED, bool EXTRA = false, bool ROWS = false>
-static void launch_attn(dim3 grid, hipStream_t st, float* ksc, float* vsc, const uint16_t* q, uint16_t* kc, uint16_t* vc,
-                        uint16_t* out, float* part, const int32_t* len_dev, int seq_len, int Hq, int Hkv, int Tmax, float scale,
-                        int chunk, const float* cos_t, const float* sin_t, float softcap = 0.f, const float* alibi = nullptr) {
-    if (ksc) {
-        hipLaunchKernelGGL((awq_decode_attn_kernel<G, FUSED, EXTRA, ROWS, true>), grid, dim3(256), 0, st, reinterpret_cast<const half_t*>(q),
-                           KV8Rows{reinterpret_cast<uint8_t*>(kc), ksc}, KV8Rows{reinterpret_cast<uint8_t*>(vc), vsc},
-                           reinterpret_cast<half_t*>(out), part, len_dev, seq_len, Hq, Hkv, Tmax, scale, chunk, cos_t, sin_t, softcap,
-                           alibi);
-        return;
+// The kernel's view of a cache.  The pointers lose their const here: only the fused form writes through them.
+template <bool KV8>
+static kv_rows_t<KV8> cache_rows(const void* cache, const float* scales) {
+    if constexpr (KV8) return KV8Rows{static_cast<uint8_t*>(const_cast<void*>(cache)), const_cast<float*>(scales)};
+    else return static_cast<half_t*>(const_cast<void*>(cache));
+}
+
+// One launch of awq_decode_attn_kernel<G, FUSED, EXTRA, ROWS, KV8>: the kernel's argument list is written here and nowhere else.
+// An fp8 cache (scales given) is a flag of every form.
+template <int G, bool FUSED, bool EXTRA, bool ROWS>
+static void launch_attn_kernel(const AwqAttnArgs& a, dim3 grid) {
+    const int chunk = 0;  // dealt in the kernel from the length it reads
+    const auto launch = [&](auto kv8) {
+        constexpr bool KV8 = decltype(kv8)::value;
+        hipLaunchKernelGGL((awq_decode_attn_kernel<G, FUSED, EXTRA, ROWS, KV8>), grid, dim3(256), 0, a.stream,
+                           reinterpret_cast<const half_t*>(a.q), cache_rows<KV8>(a.k_cache, a.k_scale),
+                           cache_rows<KV8>(a.v_cache, a.v_scale), reinterpret_cast<half_t*>(a.out), static_cast<float*>(a.workspace),
+                           a.len_dev, (int)a.seq_len, (int)a.Hq, (int)a.Hkv, (int)a.Tmax, a.scale, chunk, a.cos_t, a.sin_t,
+                           EXTRA ? a.softcap : 0.f, a.alibi);
+    };
+    if (a.k_scale) launch(std::true_type{});
+    else launch(std::false_type{});
+}
+
+enum class AttnForm { Plain, Fused, Extra };  // (soft-capping / ALiBi ride on the plain form: there is no fused + extra kernel)
+
+// the form becomes a template flag here; the fp8 cache in launch_attn_kernel
+template <int G, bool ROWS>
+static void launch_attn(AttnForm form, const AwqAttnArgs& a, dim3 grid) {
+    switch (form) {
+        case AttnForm::Extra: return launch_attn_kernel<G, false, true, ROWS>(a, grid);
+        case AttnForm::Fused: return launch_attn_kernel<G, true, false, ROWS>(a, grid);
+        case AttnForm::Plain: return launch_attn_kernel<G, false, false, ROWS>(a, grid);
     }
-    hipLaunchKernelGGL((awq_decode_attn_kernel<G, FUSED, EXTRA, ROWS>), grid, dim3(256), 0, st, reinterpret_cast<const half_t*>(q),
-                       reinterpret_cast<half_t*>(kc), reinterpret_cast<half_t*>(vc), reinterpret_cast<half_t*>(out), part,
-                       len_dev, seq_len, Hq, Hkv, Tmax, scale, chunk, cos_t, sin_t, softcap, alibi);
 }
 
 // cos_t == nullptr: plain form (q [B, Hq, D], rows [0, len) of the caches).  Otherwise the fused form:
 // q = raw qkv rows, `len_dev` / `seq_len` carry the POSITION of the new token.  rows: len_dev is [B], one word per sequence.
-int awq_launch_decode_attention(const uint16_t* q, uint16_t* k_cache, uint16_t* v_cache, uint16_t* out,
-                                const int32_t* len_dev, int seq_len, int max_len, int B, int Hq, int Hkv, int D, int Tmax,
-                                float scale, void* workspace, size_t workspace_bytes, const float* cos_t,
-                                const float* sin_t, hipStream_t st, float softcap, const float* alibi, bool rows, float* k_scale,
-                                float* v_scale) {
-    if (rows && !len_dev) return AWQ_ERR_NULL;
-    if ((k_scale == nullptr) != (v_scale == nullptr)) return AWQ_ERR_NULL;
-    if (D != 128) return AWQ_ERR_UNSUPPORTED;
-    const bool extra = softcap > 0.f || alibi != nullptr;
-    if (extra && cos_t) return AWQ_ERR_UNSUPPORTED;  // ALiBi models do not rotate; soft-capping takes the two-launch form
-    if (softcap < 0.f) return AWQ_ERR_BAD_SHAPE;
+int awq_launch_decode_attention(const AwqAttnArgs& a) {
+    const int seq_len = (int)a.seq_len, max_len = (int)a.max_len, B = (int)a.B, Hq = (int)a.Hq, Hkv = (int)a.Hkv, Tmax = (int)a.Tmax;
+    if (a.rows && !a.len_dev) return AWQ_ERR_NULL;
+    if ((a.k_scale == nullptr) != (a.v_scale == nullptr)) return AWQ_ERR_NULL;
+    if ((int)a.D != 128) return AWQ_ERR_UNSUPPORTED;
+    const bool extra = a.softcap > 0.f || a.alibi != nullptr, fused = a.cos_t != nullptr;
+    if (extra && fused) return AWQ_ERR_UNSUPPORTED;  // ALiBi models do not rotate; soft-capping takes the two-launch form
+    if (a.softcap < 0.f) return AWQ_ERR_BAD_SHAPE;
     if (B < 0 || Hq < 1 || Hkv < 1 || Hq % Hkv || Tmax < 1) return AWQ_ERR_BAD_SHAPE;
     const int G = Hq / Hkv;
     if (!(G == 1 || G == 2 || G == 4 || G == 8)) return AWQ_ERR_UNSUPPORTED;
     if (B == 0) return AWQ_OK;
-    const bool fused = cos_t != nullptr;
     // the split must not depend on a length that only the device knows: size it for max_len
-    const int len_for_split = len_dev ? max_len : seq_len + (fused ? 1 : 0);
+    const int len_for_split = a.len_dev ? max_len : seq_len + (fused ? 1 : 0);
     if (len_for_split < 1 || len_for_split > Tmax) return AWQ_ERR_BAD_SHAPE;
-    // Splits per KV head: about 128 rows each (AWQ_ATTN_ROWS; A/B on the whole-model decode, profiles/r04_attention_split_ab.txt:
-    // 128 rows 769 / 712 / 663 tok/s at 64 / 512 / 2048 tokens of context, 256 rows 772 / 657 / 564, 64 rows 768 / 694 / 589),
-    // at most ~1024 blocks (AWQ_ATTN_BLOCKS) and 64 splits (the combine kernel's one-lane-per-split step).  ONE split up to
-    // AWQ_ATTN_SINGLE = 256 rows: no partials, no combine launch at all -- what a
-    // short context pays for a 32-way split sized for the whole cache was 9.5 + 5 us per layer (profiles/r03_whole_model_gemv_
-    // kernel_stats.txt); callers that know the context on the host (modules/fused/decode.py: one hipGraph per length bucket)
-    // pass the bucket's bound as max_len.  (Both constants overridable in experiment builds: tools/attn_split_ab.py.)
-#ifndef AWQ_ATTN_BLOCKS
-#define AWQ_ATTN_BLOCKS 1024
-#endif
-#ifndef AWQ_ATTN_ROWS
-#define AWQ_ATTN_ROWS 128
-#endif
-#ifndef AWQ_ATTN_SINGLE
-#define AWQ_ATTN_SINGLE 256
-#endif
-    int splits = len_for_split <= AWQ_ATTN_SINGLE ? 1 : (len_for_split + AWQ_ATTN_ROWS - 1) / AWQ_ATTN_ROWS;
-    const int max_by_blocks = AWQ_ATTN_BLOCKS / (B * Hkv) > 1 ? AWQ_ATTN_BLOCKS / (B * Hkv) : 1;
-    if (splits > max_by_blocks) splits = max_by_blocks;
-    if (splits < 1) splits = 1;
-    if (splits > 64) splits = 64;
-    if (splits > 1 && (!workspace || workspace_bytes < awq_decode_attention_workspace_bytes_impl(B, Hq, splits))) {
-        const size_t per = awq_decode_attention_workspace_bytes_impl(B, Hq, 1);
-        splits = workspace ? (int)(workspace_bytes / per) : 1;
-        if (splits < 1) splits = 1;
-    }
-    const int chunk = 0;  // dealt in the kernel from the length it reads
+    const int splits = awq_attn_splits(len_for_split, (int64_t)B * Hkv, a.workspace ? a.workspace_bytes : 0,
+                                       awq_decode_attention_workspace_bytes_impl(B, Hq, 1));
     const dim3 grid((unsigned)splits, (unsigned)Hkv, (unsigned)B);
-    float* part = static_cast<float*>(workspace);
-#define AWQ_ATTN_CASE(GG)                                                                                                  \
-    case GG:                                                                                                               \
-        if (rows) {                                                                                                        \
-            if (extra) launch_attn<GG, false, true, true>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, \
-                                                          Tmax, scale, chunk, nullptr, nullptr, softcap, alibi);           \
-            else if (fused) launch_attn<GG, true, false, true>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, \
-                                                               Hkv, Tmax, scale, chunk, cos_t, sin_t);                     \
-            else launch_attn<GG, false, false, true>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, \
-                                                     scale, chunk, nullptr, nullptr);                                      \
-        } else if (extra) launch_attn<GG, false, true>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, \
-                                                scale, chunk, nullptr, nullptr, softcap, alibi);                            \
-        else if (fused) launch_attn<GG, true>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, scale, \
-                                         chunk, cos_t, sin_t);                                                             \
-        else launch_attn<GG, false>(grid, st, k_scale, v_scale, q, k_cache, v_cache, out, part, len_dev, seq_len, Hq, Hkv, Tmax, scale,      \
-                                    chunk, nullptr, nullptr);                                                              \
-        break;
+    const AttnForm form = extra ? AttnForm::Extra : fused ? AttnForm::Fused : AttnForm::Plain;
     switch (G) {
-        AWQ_ATTN_CASE(1)
-        AWQ_ATTN_CASE(2)
-        AWQ_ATTN_CASE(4)
-        default:
-        AWQ_ATTN_CASE(8)
+        case 1: a.rows ? launch_attn<1, true>(form, a, grid) : launch_attn<1, false>(form, a, grid); break;
+        case 2: a.rows ? launch_attn<2, true>(form, a, grid) : launch_attn<2, false>(form, a, grid); break;
+        case 4: a.rows ? launch_attn<4, true>(form, a, grid) : launch_attn<4, false>(form, a, grid); break;
+        default: a.rows ? launch_attn<8, true>(form, a, grid) : launch_attn<8, false>(form, a, grid);
     }
-#undef AWQ_ATTN_CASE
     if (hipGetLastError() != hipSuccess) return AWQ_ERR_LAUNCH;
     if (splits > 1) {
-        hipLaunchKernelGGL(awq_decode_attn_combine_kernel, dim3((unsigned)(B * Hq)), dim3(128), 0, st, part,
-                           reinterpret_cast<half_t*>(out), splits);
+        hipLaunchKernelGGL(awq_decode_attn_combine_kernel, dim3((unsigned)(B * Hq)), dim3(128), 0, a.stream,
+                           static_cast<float*>(a.workspace), reinterpret_cast<half_t*>(a.out), splits);
         if (hipGetLastError() != hipSuccess) return AWQ_ERR_LAUNCH;
     }
     return AWQ_OK;

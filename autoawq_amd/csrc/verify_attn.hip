@@ -216,11 +216,10 @@ __global__ __launch_bounds__(128) void awq_verify_attn_combine_kernel(const floa
 }
 
 template <int G, int TT>
-void launch_verify(dim3 grid, hipStream_t st, const uint16_t* q, const uint16_t* kc, const uint16_t* vc, uint16_t* out, float* part,
-                   const int32_t* pos_rows, int T, int NG, int Hq, int Hkv, int Tmax, float scale) {
-    hipLaunchKernelGGL((awq_verify_attn_kernel<G, TT>), grid, dim3(256), 0, st, reinterpret_cast<const half_t*>(q),
-                       reinterpret_cast<const half_t*>(kc), reinterpret_cast<const half_t*>(vc), reinterpret_cast<half_t*>(out), part,
-                       pos_rows, T, NG, Hq, Hkv, Tmax, scale);
+void launch_verify(const AwqAttnArgs& a, dim3 grid, int T, int NG) {
+    hipLaunchKernelGGL((awq_verify_attn_kernel<G, TT>), grid, dim3(256), 0, a.stream, reinterpret_cast<const half_t*>(a.q),
+                       static_cast<const half_t*>(a.k_cache), static_cast<const half_t*>(a.v_cache), reinterpret_cast<half_t*>(a.out),
+                       static_cast<float*>(a.workspace), a.len_dev, T, NG, (int)a.Hq, (int)a.Hkv, (int)a.Tmax, a.scale);
 }
 
 }  // namespace
@@ -232,43 +231,33 @@ static int verify_group_tokens(int G, int T) {
     return tt;
 }
 
+// token groups of one sequence: each is a block per split and KV head
+static int verify_groups(int G, int T) { return (T + verify_group_tokens(G, T) - 1) / verify_group_tokens(G, T); }
+
 int awq_verify_attention_splits_impl(int max_len, int B, int T, int Hq, int Hkv) {
-    const int ng = (T + verify_group_tokens(Hq / Hkv, T) - 1) / verify_group_tokens(Hq / Hkv, T);
-    // the decode launch's rule (decoder.hip: AWQ_ATTN_SINGLE / _ROWS / _BLOCKS), the token groups counted as blocks
-    int splits = max_len <= 256 ? 1 : (max_len + 127) / 128;
-    const int by_blocks = 1024 / (B * Hkv * ng) > 1 ? 1024 / (B * Hkv * ng) : 1;
-    if (splits > by_blocks) splits = by_blocks;
-    if (splits > 64) splits = 64;
-    return splits < 1 ? 1 : splits;
+    return awq_attn_splits(max_len, (int64_t)B * Hkv * verify_groups(Hq / Hkv, T));
 }
 
 size_t awq_verify_attention_workspace_bytes_impl(int B, int T, int Hq, int splits) {
     return (size_t)B * T * Hq * splits * (128 + 2) * sizeof(float);
 }
 
-int awq_launch_verify_attention(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
-                                const int32_t* pos_rows, int max_len, int B, int T, int Hq, int Hkv, int D, int Tmax, float scale,
-                                void* workspace, size_t workspace_bytes, hipStream_t st) {
-    if (!pos_rows) return AWQ_ERR_NULL;
+int awq_launch_verify_attention(const AwqAttnArgs& a, int T) {
+    const int max_len = (int)a.max_len, B = (int)a.B, Hq = (int)a.Hq, Hkv = (int)a.Hkv, Tmax = (int)a.Tmax;
+    if (!a.len_dev) return AWQ_ERR_NULL;
     if (B < 0 || Hq < 1 || Hkv < 1 || Hq % Hkv || Tmax < 1) return AWQ_ERR_BAD_SHAPE;
-    if (D != 128 || T < 2 || T > 8) return AWQ_ERR_UNSUPPORTED;
+    if ((int)a.D != 128 || T < 2 || T > 8) return AWQ_ERR_UNSUPPORTED;
     const int G = Hq / Hkv;
     if (!(G == 1 || G == 2 || G == 4 || G == 8)) return AWQ_ERR_UNSUPPORTED;
     if (max_len < T || max_len > Tmax) return AWQ_ERR_BAD_SHAPE;
     if (B == 0) return AWQ_OK;
-    const int TT = verify_group_tokens(G, T), NG = (T + TT - 1) / TT;
+    const int TT = verify_group_tokens(G, T), NG = verify_groups(G, T);
     if ((int64_t)B * NG > 65535) return AWQ_ERR_BAD_SHAPE;
-    int splits = awq_verify_attention_splits_impl(max_len, B, T, Hq, Hkv);
-    if (splits > 1 && (!workspace || workspace_bytes < awq_verify_attention_workspace_bytes_impl(B, T, Hq, splits))) {
-        const size_t per = awq_verify_attention_workspace_bytes_impl(B, T, Hq, 1);
-        splits = workspace ? (int)(workspace_bytes / per) : 1;
-        if (splits < 1) splits = 1;
-    }
+    const int splits = awq_attn_splits(max_len, (int64_t)B * Hkv * NG, a.workspace ? a.workspace_bytes : 0,
+                                       awq_verify_attention_workspace_bytes_impl(B, T, Hq, 1));
     const dim3 grid((unsigned)splits, (unsigned)Hkv, (unsigned)(B * NG));
-    float* part = static_cast<float*>(workspace);
-#define AWQ_VERIFY_CASE(GG, TTT)                                                                                          \
-    if (G == GG && TT == TTT)                                                                                             \
-        launch_verify<GG, TTT>(grid, st, q, k_cache, v_cache, out, part, pos_rows, T, NG, Hq, Hkv, Tmax, scale);
+#define AWQ_VERIFY_CASE(GG, TTT) \
+    if (G == GG && TT == TTT) launch_verify<GG, TTT>(a, grid, T, NG);
     AWQ_VERIFY_CASE(1, 2)
     AWQ_VERIFY_CASE(1, 4)
     AWQ_VERIFY_CASE(1, 8)
@@ -279,8 +268,8 @@ int awq_launch_verify_attention(const uint16_t* q, const uint16_t* k_cache, cons
 #undef AWQ_VERIFY_CASE
     if (hipGetLastError() != hipSuccess) return AWQ_ERR_LAUNCH;
     if (splits > 1) {
-        hipLaunchKernelGGL(awq_verify_attn_combine_kernel, dim3((unsigned)((int64_t)B * T * Hq)), dim3(128), 0, st, part,
-                           reinterpret_cast<half_t*>(out), splits);
+        hipLaunchKernelGGL(awq_verify_attn_combine_kernel, dim3((unsigned)((int64_t)B * T * Hq)), dim3(128), 0, a.stream,
+                           static_cast<float*>(a.workspace), reinterpret_cast<half_t*>(a.out), splits);
         if (hipGetLastError() != hipSuccess) return AWQ_ERR_LAUNCH;
     }
     return AWQ_OK;

@@ -714,6 +714,24 @@ def _kv8(name, k_cache, v_cache, k_scale, v_scale):
     return True
 
 
+def _kv_ptrs(kv8, k_cache, v_cache, k_scale, v_scale):
+    """the cache arguments of an attention entry point: the *_fp8 forms take the scale arrays after the caches"""
+    return [_ptr(k_cache), _ptr(v_cache)] + ([_ptr(k_scale), _ptr(v_scale)] if kv8 else [])
+
+
+def _stream_workspace(table, device, need):
+    """The scratch tensor of `table` for (device, current stream), at least `need` bytes.  One that has to grow retires the old
+    tensor into _retired_raw: a captured graph may still hold it."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), _stream())
+    ws = table.get(key)
+    if ws is None or ws.numel() < need:
+        if ws is not None:
+            _retired_raw.append(ws)
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        table[key] = ws
+    return ws
+
+
 def rope_kv_append(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n_kv_heads, head_dim, rotary_dim, pos_dev=None,
                    pos_rows=None, k_scale=None, v_scale=None):
     """qkv [B, S, (Hq + 2 Hkv) * D] fp16 -> rotated q [B, S, Hq, D]; rotated k and v are written into
@@ -727,30 +745,15 @@ def rope_kv_append(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n_kv_hea
     q = torch.empty((B, S, n_heads, head_dim), dtype=torch.float16, device=qkv.device)
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()) or k_cache.shape[0] < B:
         raise _lib.AwqHipError("rope_kv_append: caches must be contiguous [>=B, Tmax, Hkv, D]")
-    if kv8:
-        L = _lib.lib()
-        with torch.cuda.device(qkv.device):
-            if pos_rows is not None:
-                _check_rows("rope_kv_append", "pos", pos_rows, pos_dev, B, qkv.device)
-                _lib.check(L.awq_rope_kv_append_rows_fp8(_ptr(qkv), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
-                                                         _ptr(cos), _ptr(sin), _ptr(pos_rows), B, S, n_heads, n_kv_heads, head_dim,
-                                                         rotary_dim, k_cache.shape[1], _stream()), "awq_rope_kv_append_rows_fp8")
-            else:
-                _lib.check(L.awq_rope_kv_append_fp8(_ptr(qkv), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
-                                                    _ptr(cos), _ptr(sin), _ptr(pos_dev), int(start_pos), B, S, n_heads, n_kv_heads,
-                                                    head_dim, rotary_dim, k_cache.shape[1], _stream()), "awq_rope_kv_append_fp8")
-        return q
-    if pos_rows is not None:
+    rows = pos_rows is not None
+    if rows:
         _check_rows("rope_kv_append", "pos", pos_rows, pos_dev, B, qkv.device)
-        with torch.cuda.device(qkv.device):
-            _lib.check(_lib.lib().awq_rope_kv_append_rows(_ptr(qkv), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(cos), _ptr(sin),
-                                                          _ptr(pos_rows), B, S, n_heads, n_kv_heads, head_dim, rotary_dim,
-                                                          k_cache.shape[1], _stream()), "awq_rope_kv_append_rows")
-        return q
+    name = "awq_rope_kv_append" + ("_rows" if rows else "") + ("_fp8" if kv8 else "")
     with torch.cuda.device(qkv.device):
-        _lib.check(_lib.lib().awq_rope_kv_append(_ptr(qkv), _ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(cos), _ptr(sin),
-                                                 _ptr(pos_dev), int(start_pos), B, S, n_heads, n_kv_heads, head_dim,
-                                                 rotary_dim, k_cache.shape[1], _stream()), "awq_rope_kv_append")
+        _lib.check(getattr(_lib.lib(), name)(
+            _ptr(qkv), _ptr(q), *_kv_ptrs(kv8, k_cache, v_cache, k_scale, v_scale), _ptr(cos), _ptr(sin),
+            *([_ptr(pos_rows)] if rows else [_ptr(pos_dev), int(start_pos)]),
+            B, S, n_heads, n_kv_heads, head_dim, rotary_dim, k_cache.shape[1], _stream()), name)
     return q
 
 
@@ -795,53 +798,27 @@ def decode_attention(q, k_cache, v_cache, seq_len, scale=None, len_dev=None, max
     Hkv, Tmax = k_cache.shape[2], k_cache.shape[1]
     q = q.contiguous()
     out = torch.empty_like(q)
-    L = _lib.lib()
-    key = (q.device.index if q.device.index is not None else torch.cuda.current_device(), _stream())
-    need = L.awq_decode_attention_workspace_bytes(B, Hq)
-    ws = _attn_workspaces.get(key)
-    if ws is None or ws.numel() < need:
-        if ws is not None:
-            _retired_raw.append(ws)
-        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-        _attn_workspaces[key] = ws
+    ws = _stream_workspace(_attn_workspaces, q.device, _lib.lib().awq_decode_attention_workspace_bytes(B, Hq))
     if scale is None:
         scale = D ** -0.5
     if alibi_slopes is not None:
         alibi_slopes = alibi_slopes.to(torch.float32).contiguous()
         if alibi_slopes.numel() != Hq:
             raise _lib.AwqHipError("decode_attention: alibi_slopes must hold one slope per query head")
-    if kv8:
-        with torch.cuda.device(q.device):
-            if len_rows is not None:
-                _check_rows("decode_attention", "len", len_rows, len_dev, B, q.device)
-                _lib.check(L.awq_decode_attention_rows_fp8(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(out),
-                                                           _ptr(len_rows), int(max_len if max_len is not None else Tmax), B, Hq, Hkv, D,
-                                                           Tmax, float(scale), float(softcap), _ptr(alibi_slopes), _ptr(ws), ws.numel(),
-                                                           _stream()), "awq_decode_attention_rows_fp8")
-            else:
-                _lib.check(L.awq_decode_attention_ex_fp8(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(out),
-                                                         _ptr(len_dev), int(seq_len), int(max_len if max_len is not None else seq_len),
-                                                         B, Hq, Hkv, D, Tmax, float(scale), float(softcap), _ptr(alibi_slopes),
-                                                         _ptr(ws), ws.numel(), _stream()), "awq_decode_attention_ex_fp8")
-        return out
-    if len_rows is not None:
+    rows = len_rows is not None
+    if rows:
         _check_rows("decode_attention", "len", len_rows, len_dev, B, q.device)
-        with torch.cuda.device(q.device):
-            _lib.check(L.awq_decode_attention_rows(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(len_rows),
-                                                   int(max_len if max_len is not None else Tmax), B, Hq, Hkv, D, Tmax,
-                                                   float(scale), float(softcap), _ptr(alibi_slopes), _ptr(ws), ws.numel(),
-                                                   _stream()), "awq_decode_attention_rows")
-        return out
+    # the rows and fp8 forms take softcap / alibi_slopes themselves; fp16 with the shared word has the _ex entry for them
+    extra = rows or kv8 or bool(softcap) or alibi_slopes is not None
+    name = "awq_decode_attention" + ("_rows" if rows else "_ex" if extra else "") + ("_fp8" if kv8 else "")
+    if max_len is None:
+        max_len = Tmax if rows else seq_len
     with torch.cuda.device(q.device):
-        if softcap or alibi_slopes is not None:
-            _lib.check(L.awq_decode_attention_ex(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(len_dev), int(seq_len),
-                                                 int(max_len if max_len is not None else seq_len), B, Hq, Hkv, D, Tmax,
-                                                 float(scale), float(softcap), _ptr(alibi_slopes), _ptr(ws), ws.numel(),
-                                                 _stream()), "awq_decode_attention_ex")
-        else:
-            _lib.check(L.awq_decode_attention(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(len_dev), int(seq_len),
-                                              int(max_len if max_len is not None else seq_len), B, Hq, Hkv, D, Tmax,
-                                              float(scale), _ptr(ws), ws.numel(), _stream()), "awq_decode_attention")
+        _lib.check(getattr(_lib.lib(), name)(
+            _ptr(q), *_kv_ptrs(kv8, k_cache, v_cache, k_scale, v_scale), _ptr(out),
+            *([_ptr(len_rows)] if rows else [_ptr(len_dev), int(seq_len)]), int(max_len),
+            B, Hq, Hkv, D, Tmax, float(scale), *([float(softcap), _ptr(alibi_slopes)] if extra else []),
+            _ptr(ws), ws.numel(), _stream()), name)
     return out
 
 
@@ -859,47 +836,20 @@ def decode_attention_rope(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n
     D = k_cache.shape[3]
     qkv = qkv.contiguous()
     out = torch.empty((B, n_heads, D), dtype=torch.float16, device=qkv.device)
-    L = _lib.lib()
-    key = (qkv.device.index if qkv.device.index is not None else torch.cuda.current_device(), _stream())
-    need = L.awq_decode_attention_workspace_bytes(B, n_heads)
-    ws = _attn_workspaces.get(key)
-    if ws is None or ws.numel() < need:
-        if ws is not None:
-            _retired_raw.append(ws)
-        ws = torch.empty(need, dtype=torch.uint8, device=qkv.device)
-        _attn_workspaces[key] = ws
+    ws = _stream_workspace(_attn_workspaces, qkv.device, _lib.lib().awq_decode_attention_workspace_bytes(B, n_heads))
     if scale is None:
         scale = D ** -0.5
-    if kv8:
-        with torch.cuda.device(qkv.device):
-            if pos_rows is not None:
-                _check_rows("decode_attention_rope", "pos", pos_rows, pos_dev, B, qkv.device)
-                _lib.check(L.awq_decode_attention_rope_rows_fp8(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
-                                                                _ptr(cos), _ptr(sin), _ptr(out), _ptr(pos_rows),
-                                                                int(max_len if max_len is not None else k_cache.shape[1]), B, n_heads,
-                                                                n_kv_heads, D, k_cache.shape[1], float(scale), _ptr(ws), ws.numel(),
-                                                                _stream()), "awq_decode_attention_rope_rows_fp8")
-            else:
-                _lib.check(L.awq_decode_attention_rope_fp8(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
-                                                           _ptr(cos), _ptr(sin), _ptr(out), _ptr(pos_dev), int(start_pos),
-                                                           int(max_len if max_len is not None else start_pos + 1), B, n_heads,
-                                                           n_kv_heads, D, k_cache.shape[1], float(scale), _ptr(ws), ws.numel(),
-                                                           _stream()), "awq_decode_attention_rope_fp8")
-        return out
-    if pos_rows is not None:
+    rows = pos_rows is not None
+    if rows:
         _check_rows("decode_attention_rope", "pos", pos_rows, pos_dev, B, qkv.device)
-        with torch.cuda.device(qkv.device):
-            _lib.check(L.awq_decode_attention_rope_rows(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(cos), _ptr(sin), _ptr(out),
-                                                        _ptr(pos_rows), int(max_len if max_len is not None else k_cache.shape[1]),
-                                                        B, n_heads, n_kv_heads, D, k_cache.shape[1], float(scale), _ptr(ws),
-                                                        ws.numel(), _stream()), "awq_decode_attention_rope_rows")
-        return out
+    name = "awq_decode_attention_rope" + ("_rows" if rows else "") + ("_fp8" if kv8 else "")
+    if max_len is None:
+        max_len = k_cache.shape[1] if rows else start_pos + 1
     with torch.cuda.device(qkv.device):
-        _lib.check(L.awq_decode_attention_rope(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(cos), _ptr(sin), _ptr(out),
-                                               _ptr(pos_dev), int(start_pos),
-                                               int(max_len if max_len is not None else start_pos + 1), B, n_heads,
-                                               n_kv_heads, D, k_cache.shape[1], float(scale), _ptr(ws), ws.numel(),
-                                               _stream()), "awq_decode_attention_rope")
+        _lib.check(getattr(_lib.lib(), name)(
+            _ptr(qkv), *_kv_ptrs(kv8, k_cache, v_cache, k_scale, v_scale), _ptr(cos), _ptr(sin), _ptr(out),
+            *([_ptr(pos_rows)] if rows else [_ptr(pos_dev), int(start_pos)]), int(max_len),
+            B, n_heads, n_kv_heads, D, k_cache.shape[1], float(scale), _ptr(ws), ws.numel(), _stream()), name)
     return out
 
 
@@ -1246,14 +1196,7 @@ def verify_attention_rows(q, k_cache, v_cache, pos_rows, max_len=None, scale=Non
     q = q.contiguous()
     out = torch.empty_like(q)
     L = _lib.lib()
-    key = (q.device.index if q.device.index is not None else torch.cuda.current_device(), _stream())
-    need = L.awq_verify_attention_workspace_bytes(B, T, Hq)
-    ws = _verify_workspaces.get(key)
-    if ws is None or ws.numel() < need:
-        if ws is not None:
-            _retired_raw.append(ws)  # a captured graph may still hold it
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=q.device)
-        _verify_workspaces[key] = ws
+    ws = _stream_workspace(_verify_workspaces, q.device, max(L.awq_verify_attention_workspace_bytes(B, T, Hq), 16))
     if scale is None:
         scale = D ** -0.5
     with torch.cuda.device(q.device):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Decode attention: how many sequence splits?  Builds csrc/decoder.hip with other (blocks in flight, rows per split beyond the
-single-split length of 256) targets into tools/bin/ and times the whole 7B-shape decoder (tools/bench_decode_model.py, GEMV layout) with each library.
+"""Decode attention: how many sequence splits?  Builds csrc/decoder.hip and csrc/verify_attn.hip with other (blocks in flight,
+rows per split beyond the single-split length of 256) targets into tools/bin/ and times the whole 7B-shape decoder (tools/bench_decode_model.py, GEMV layout) with each library.
     python tools/attn_split_ab.py --build-only   (here)      gpurun -- python tools/attn_split_ab.py"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,14 +15,17 @@ def so(v):
 
 def build():
     os.makedirs(os.path.join(ROOT, "tools", "bin"), exist_ok=True)
-    others = [os.path.join(CSRC, "build", f[:-4] + ".o") for f in sorted(os.listdir(CSRC)) if f.endswith(".hip") and f != "decoder.hip"]
+    variant = ("decoder.hip", "verify_attn.hip")  # the split rule (csrc/awq_internal.h: awq_attn_splits) is compiled into both launchers
+    others = [os.path.join(CSRC, "build", f[:-4] + ".o") for f in sorted(os.listdir(CSRC)) if f.endswith(".hip") and f not in variant]
     for v in sorted(set(VARIANTS[1:]) - {VARIANTS[0]}):
-        obj = os.path.join(ROOT, "tools", "bin", "decoder_x.o")
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
-                               "-fno-slp-vectorize", "-Wno-inline-asm", f"-DAWQ_ATTN_BLOCKS={v[0]}", f"-DAWQ_ATTN_ROWS={v[1]}", f"-DAWQ_ATTN_NO_EARLY={v[2] & 1}", f"-DAWQ_ATTN_NO_DPP={v[2] >> 1}",
-                               "-DAWQ_BUILDING_LIB", "-I" + os.path.join(ROOT, "include"), "-c", os.path.join(CSRC, "decoder.hip"), "-o", obj])
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so(v), obj] + others)
-        os.remove(obj)
+        objs = [os.path.join(ROOT, "tools", "bin", f[:-4] + "_x.o") for f in variant]
+        for f, obj in zip(variant, objs):
+            subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
+                                   "-fno-slp-vectorize", "-Wno-inline-asm", f"-DAWQ_ATTN_BLOCKS={v[0]}", f"-DAWQ_ATTN_ROWS={v[1]}", f"-DAWQ_ATTN_NO_EARLY={v[2] & 1}", f"-DAWQ_ATTN_NO_DPP={v[2] >> 1}",
+                                   "-DAWQ_BUILDING_LIB", "-I" + os.path.join(ROOT, "include"), "-c", os.path.join(CSRC, f), "-o", obj])
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so(v)] + objs + others)
+        for obj in objs:
+            os.remove(obj)
 
 
 def child(i):
