@@ -82,12 +82,24 @@ int awq_launch_gemm_regb(const AwqGemmArgs& a, int bm);
 // Batched-decode GEMM, 17 <= M <= 64, weights decoded in registers, no barrier in the K loop (gemm_skinny.hip).
 bool awq_gemm_skinny_supports(int M, int K, int N, int g);
 int awq_launch_gemm_skinny(const AwqGemmArgs& a, int splitk);
-// GEMV layout (qweight [N, K/8], qzeros [N, ZW], scales [N, 8*ZW]): MFMA GEMV, M <= 16, and the
-// bit-exact dequant to W^T [N, K].  nwaves (4|8|16) / unroll (4|8): 0 = auto.
+// The arguments of a launch on the GEMV layout (qweight int32 [N, K/8], qzeros int32 [N, ZW], scales fp16 [N, 8 ZW]) or the GEMVFast
+// layout (qweight int16 [N/4, K], scales / qzeros fp16 [group_rows, N], qzeros = -(s z)): capi.hip checks what the C ABI passes,
+// narrows the sizes and fills this once.  The layout is the launcher's; a kernel's tuning integers stay its launcher's parameters.
+struct AwqGemvArgs {
+    const uint16_t* x;       // [M, K] fp16 (the dequant launchers: not read)
+    const void* qweight;     // the layout's packed words (awq_launch_gemm_regb_fz: GEMM-layout words [K, N/8], a repacked temporary)
+    const uint16_t* scales;
+    const void* qzeros;      // GEMV: packed zero nibbles; GEMVFast: fp16 zero terms
+    uint16_t* y;             // [M, N] fp16 (the dequant launchers: W^T [N, K])
+    int M, K, N, g;
+    int width;               // GEMV: zeros_width ZW (words of zero nibbles per row); GEMVFast: group_rows (rows of scales / qzeros)
+    hipStream_t stream;
+};
+
+// GEMV layout: MFMA GEMV, M <= 16, and the bit-exact dequant to W^T [N, K].  nwaves (4|8|16) / unroll (4|8): 0 = auto.
 bool awq_gemv_nk_supports(int M, int K, int N, int g);
 size_t awq_gemv_nk_lds_bytes(int M, int K, int ZW, int nwaves);
-int awq_launch_gemv_nk(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
-                       uint16_t* y, int M, int K, int N, int g, int ZW, int nwaves, int unroll, hipStream_t st);
+int awq_launch_gemv_nk(const AwqGemvArgs& a, int nwaves, int unroll);
 // GEMV layout, row-streaming VALU kernel (gemv_rows.hip), M <= 4: waves per block (<= 8), super-units in flight per wave
 // (1|2), blocks per CU, 1-KiB slots of a row per wave (1|2|3|4|6|8); 0 = auto each.
 bool awq_gemv_rows_supports(int M, int K, int N, int g);
@@ -104,41 +116,33 @@ struct AwqRowsFx {  // decoder-block prologue / epilogue of the row-streaming ke
     int first_expert = 0;                  // pair_expert holds global ids; the stack holds experts [first_expert, first_expert + num_experts)
     int parts = 0;                         // blocks one expert matrix is dealt over (0 = auto)
 };
-int awq_launch_gemv_rows(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
-                         uint16_t* y, int M, int K, int N, int g, int ZW, int waves, int depth, int bpc, int sl, hipStream_t st,
-                         const AwqRowsFx* fx = nullptr);
+int awq_launch_gemv_rows(const AwqGemvArgs& a, int waves, int depth, int bpc, int sl, const AwqRowsFx* fx = nullptr);
 // GEMV layout, 2 <= M <= 16 while the activations fit LDS as MFMA fragments (M K <= 32768; M <= 8 at K = 4096): weights stream
 // through LDS by DMA into v_mfma_f32_16x16x32_f16 (gemv_lds.hip).  ks: waves per tile (1|2|4), depth: pieces in flight; 0 = auto.
 bool awq_gemv_lds_supports(int M, int K, int N, int g);
-int awq_launch_gemv_lds(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* y,
-                        int M, int K, int N, int g, int ZW, int ks, int depth, hipStream_t st);
+int awq_launch_gemv_lds(const AwqGemvArgs& a, int ks, int depth);
 // GEMV layout, 1 <= M <= 32 per launch, group_size 128: activations as MFMA A fragments in registers, the K range of a 16-row tile
 // split over the waves of one block, weights by LDS-DMA (gemv_batch.hip).  form: activations through a wave-private LDS staging area
 // (1) or by direct fragment loads (2); depth: pieces in flight per wave (1..3); 0 = auto.
 bool awq_gemv_batch_supports(int M, int K, int N, int g);
-int awq_launch_gemv_batch(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* y,
-                          int M, int K, int N, int g, int ZW, int form, int depth, hipStream_t st);
+int awq_launch_gemv_batch(const AwqGemvArgs& a, int form, int depth);
 // the same kernel on the GEMVFast layout's buffers (N % 16 == 0)
 bool awq_gemv_batch_fast_supports(int M, int K, int N, int g);
-int awq_launch_gemv_batch_fast(const uint16_t* x, const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros, uint16_t* y,
-                               int M, int K, int N, int g, int group_rows, int depth, hipStream_t st);
+int awq_launch_gemv_batch_fast(const AwqGemvArgs& a, int depth);
 // host only: the plan of a launch (awq_gemv_batch_plan); false where the planner refuses the arguments
 bool awq_gemv_batch_plan_fill(int M, int K, int N, int g, int form, int depth, bool fast, int32_t* out);
 // GEMV layout, prefill-sized batches: the register-decoded MFMA GEMM reading the layout's own buffers (gemm_regb.hip, NK form)
 bool awq_gemm_regb_nk_supports(int M, int K, int N, int g, int ZW);
-int awq_launch_gemm_regb_nk(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
-                            const uint16_t* bias, uint16_t* y, int M, int K, int N, int g, int ZW, int bm, hipStream_t st);
+int awq_launch_gemm_regb_nk(const AwqGemvArgs& a, int bm);
 // GEMM-layout words + the GEMVFast format's scales / fp16 zero terms [>= K/g, N] (gemm_regb.hip, FZ form: W = fp16(w s + qzeros))
-int awq_launch_gemm_regb_fz(const uint16_t* x, const int32_t* qweight_kn, const uint16_t* scales, const uint16_t* qzeros_f16, uint16_t* y,
-                            int M, int K, int N, int g, int bm, hipStream_t st);
+int awq_launch_gemm_regb_fz(const AwqGemvArgs& a, int bm);
 // MoE prefill: the same kernel over a token list sorted by expert (device-side row offsets), GEMM-layout expert stacks
 int awq_launch_gemm_regb_grouped(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
                                  uint16_t* y, const int32_t* seg, int P, int E, int K, int N, int g, int bm, hipStream_t st,
                                  const int32_t* row_map = nullptr, int x_div = 1, const float* pair_w = nullptr, int gather = 0,
                                  int scatter = 0);
 int awq_launch_moe_sort(const int* ids, int P, int E, int* order, int* seg, hipStream_t st);
-int awq_launch_dequant_nk(const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* out, int K,
-                          int N, int g, int ZW, hipStream_t st);
+int awq_launch_dequant_nk(const AwqGemvArgs& a);
 // Grouped (MoE) GEMM over stacked expert tensors (awq/modules/fused/moe.py:60-89), M = 16-row token blocks.
 size_t awq_grouped_workspace_bytes_impl(int max_blocks, int K, int N);
 int awq_launch_grouped_gemm(const AwqGemmArgs& a, const int* sorted_ids, const int* expert_ids, const int* num_post_pad,
@@ -149,10 +153,8 @@ int awq_launch_silu_and_mul(const uint16_t* in, uint16_t* out, int64_t rows, int
 // GEMVFast layout (qweight int16 [N/4, K], scales / qzeros fp16 [8*ZW, N], qzeros = -(s*z)).
 bool awq_gemv_fast_supports(int M, int K, int N, int g);
 size_t awq_gemv_fast_lds_bytes(int M, int K, int g, int nwaves);
-int awq_launch_gemv_fast(const uint16_t* x, const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros,
-                         uint16_t* y, int M, int K, int N, int g, int GP, int nwaves, int unroll, hipStream_t st);
-int awq_launch_dequant_fast(const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros, uint16_t* out, int K,
-                            int N, int g, hipStream_t st);
+int awq_launch_gemv_fast(const AwqGemvArgs& a, int nwaves, int unroll);
+int awq_launch_dequant_fast(const AwqGemvArgs& a);
 // MoE routing (softmax + top-k + block alignment) in one launch; T tokens, E <= 64 experts, k <= 8.
 int awq_launch_moe_route(const float* logits, float* topk_w, int* topk_ids, int* sorted_ids, int* expert_ids,
                          int* num_post_pad, int T, int E, int k, int renorm, int block, int first_expert, int num_local,

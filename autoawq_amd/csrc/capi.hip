@@ -395,30 +395,124 @@ int awq_grouped_gemm_prefill_ex(const uint16_t* x, const int32_t* qweight, const
                                         (int)x_div, pair_weights, gather ? 1 : 0, scatter ? 1 : 0);
 }
 
-/* ---- GEMV layout ------------------------------------------------------------------------- */
+}  // extern "C"
 
-// Which kernel awq_gemv_forward's AUTO dispatch takes (host only, no launch): the row-streaming kernel at batches 1 and 2, and at
-// batches 3 .. 4 while K <= 6144 (profiles/r03_gemv_rows_sweep.txt); the LDS-streaming MFMA kernel from five
-// batch rows on matrices of 8192 rows and more (4096 x 11008, M = 8: 11.6 us vs 19.0 for the tile kernel; 4096 x 22016: 16.7 vs
-// 35.7; below that the tile kernel is level or ahead); the 16-row MFMA tile kernel otherwise.  -1: no kernel takes the shape.
+/* ---- GEMV and GEMVFast layouts: an entry point checks what only it takes, calls its layout's checker (the shape rule, the required
+ * pointers and their alignment; it fills the launch's arguments), asks the layout's dispatch what the call launches, and launches it */
+namespace {
+// the one place where the sizes are narrowed: after the checkers' range checks (the two dequantisers have none, as published)
+AwqGemvArgs gemv_args(const uint16_t* x, const void* qweight, const uint16_t* scales, const void* qzeros, uint16_t* y, int64_t M,
+                      int64_t K, int64_t N, int64_t g, int64_t width, void* stream) {
+    return {x, qweight, scales, qzeros, y, (int)M, (int)K, (int)N, (int)g, (int)width, static_cast<hipStream_t>(stream)};
+}
+
+inline bool empty(const AwqGemvArgs& a) { return a.M == 0 || a.N == 0; }
+
+// GEMV layout: the shape rule; then, unless the call is empty (the caller returns AWQ_OK on empty(*a)), the five pointers and the
+// alignment of x, qweight and scales.  own_present / own_aligned: the entry point's verdict on the pointers only it takes or checks
+// -- awq_gemv_forward looks at y's alignment for the PREFILL kernel alone, awq_gemv_forward_ex at its norm weight's, the grouped
+// entry requires its pair list; nobody looks at qzeros'.  An entry point's own shape checks answer AWQ_ERR_BAD_SHAPE like the rule,
+// so they run before this; what it refuses with AWQ_ERR_UNSUPPORTED (_ex: M != 1; grouped: its limits) comes after: as published.
+int check_gemv(AwqGemvArgs* a, const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* y,
+               int64_t M, int64_t K, int64_t N, int64_t g, int64_t ZW, void* stream, bool own_present = true, bool own_aligned = true) {
+    if (K <= 0 || N < 0 || g <= 0 || K % g || K % 8 || ZW <= 0 || ZW * 8 < K / g) return AWQ_ERR_BAD_SHAPE;
+    if (M < 0 || M > INT32_MAX || K > INT32_MAX || N > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    *a = gemv_args(x, qweight, scales, qzeros, y, M, K, N, g, ZW, stream);
+    if (empty(*a)) return AWQ_OK;
+    if (!x || !qweight || !scales || !qzeros || !y || !own_present) return AWQ_ERR_NULL;
+    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales) || !own_aligned) return AWQ_ERR_BAD_ALIGNMENT;
+    return AWQ_OK;
+}
+
+// GEMVFast layout: as above; qzeros (fp16 terms here) is aligned too.  awq_gemv_fast_prefill: own_* = its temporary and y.
+int check_gemv_fast(AwqGemvArgs* a, const uint16_t* x, const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros,
+                    uint16_t* y, int64_t M, int64_t K, int64_t N, int64_t g, int64_t group_rows, void* stream, bool own_present = true,
+                    bool own_aligned = true) {
+    if (K <= 0 || N < 0 || g <= 0 || K % g || N % 4 || K % 64 || group_rows < K / g) return AWQ_ERR_BAD_SHAPE;
+    if (M < 0 || M > INT32_MAX || K > INT32_MAX || N > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    *a = gemv_args(x, qweight, scales, qzeros, y, M, K, N, g, group_rows, stream);
+    if (empty(*a)) return AWQ_OK;
+    if (!x || !qweight || !scales || !qzeros || !y || !own_present) return AWQ_ERR_NULL;
+    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales) || !aligned16(qzeros) || !own_aligned) return AWQ_ERR_BAD_ALIGNMENT;
+    return AWQ_OK;
+}
+
+// What a call launches: the kernel (-1: none takes it, AWQ_ERR_UNSUPPORTED) and, for the batched kernel, the rows per launch.
+struct GemvPlan { int kernel, rows; };
+const GemvPlan no_kernel{-1, 0};
+
+// The batched kernel (gemv_batch.hip) runs any M in launches of at most 128 rows (up to four row parts of <= 32 rows, each in its
+// own block, the blocks of a tile list residents of one XCD so that the matrix is fetched from HBM once); where the parts do not fit
+// the LDS budget (very long tile lists per block) launches of fewer rows.  The rows per launch, balanced; 0: the kernel refuses.
+int batch_rows(bool (*supports)(int, int, int, int), int M, int K, int N, int g) {
+    int cap = 128;
+    while (cap > 32 && !supports(M > cap ? cap : M, K, N, g)) cap /= 2;
+    if (!supports(M > cap ? cap : M, K, N, g)) return 0;
+    const int nchunk = (M + cap - 1) / cap;
+    return (M + nchunk - 1) / nchunk;
+}
+
+template <class Launch>
+int launch_row_chunks(const AwqGemvArgs& a, int rows, Launch launch) {
+    for (int64_t m0 = 0; m0 < a.M; m0 += rows) {
+        AwqGemvArgs c = a;
+        c.x += m0 * a.K, c.y += m0 * a.N;
+        c.M = (int)(a.M - m0 < rows ? a.M - m0 : rows);
+        if (const int rc = launch(c)) return rc;
+    }
+    return AWQ_OK;
+}
+
+// The dispatch of awq_gemv_forward (host only, no launch).  AUTO:
+//  - the batched kernel (activations in registers, the K range split over the waves of a block, weights by LDS-DMA) wherever it
+//    takes the shape (group_size 128) from five rows, four while K > 2048, three where the row-streaming kernel is not the choice
+//    (K > 6144): it costs the same at 1 .. 5 rows while gemv_rows / gemv_nk grow by ~1 us per row
+//    (profiles/r05_sweep_small_batch.txt, M = 4: 9.1 vs 10.3 us at 4096 x 11008, 14.4 vs 15.3 at 4096 x 22016, 12.7 vs 17.6 at
+//    8192 x 7168; level at K = 11008; behind at K = 1024); 4096 x 11008, M = 8: see profiles/r05_*;
+//  - the row-streaming kernel at batches 1 and 2 and at batches 3 .. 4 while K <= 6144: ahead of the 16-row tile kernel there on
+//    all four 7B shapes (profiles/r03_gemv_rows_sweep.txt: M = 2 4.65 / 7.05 / 10.77 / 8.57 us vs 6.18 / 9.96 / 16.65 / 10.73;
+//    M = 4 at K = 4096 5.79 / 9.79 / 14.39 vs 6.59 / 10.40 / 18.29; at K = 11008 12.25 vs 11.79);
+//  - the LDS-streaming MFMA kernel from five rows on matrices of 8192 rows and more (4096 x 11008, M = 8: 11.6 us vs 19.0 for the
+//    tile kernel; 4096 x 22016: 16.7 vs 35.7; below that the tile kernel is level or ahead);
+//  - the 16-row MFMA tile kernel otherwise.  PREFILL is explicit only.
+// A kernel the caller names is not replaced where it refuses the shape (ROWS, LDS, BATCH: no kernel); a number that names none runs
+// the tile kernel.  All but the batched kernel take at most 16 rows per call (the host wrapper chunks).
+GemvPlan gemv_plan(uint32_t kern, int M, int K, int N, int g) {
+    if (kern == AWQ_GEMV_KERNEL_PREFILL) return {(int)kern, M};
+    if (kern == AWQ_GEMV_KERNEL_BATCH || (kern == AWQ_GEMV_KERNEL_AUTO && (M >= 5 || (M == 4 && K > 2048) || (M == 3 && K > 6144)) &&
+                                          awq_gemv_batch_supports(M > 32 ? 32 : M, K, N, g))) {
+        const int rows = batch_rows(awq_gemv_batch_supports, M, K, N, g);
+        return rows ? GemvPlan{(int)AWQ_GEMV_KERNEL_BATCH, rows} : no_kernel;
+    }
+    if (M > 16) return no_kernel;
+    if (kern == AWQ_GEMV_KERNEL_AUTO) {
+        if ((M <= 2 || (M <= 4 && K <= 6144)) && awq_gemv_rows_supports(M, K, N, g)) kern = AWQ_GEMV_KERNEL_ROWS;
+        else if (M >= 5 && N >= 8192 && awq_gemv_lds_supports(M, K, N, g)) kern = AWQ_GEMV_KERNEL_LDS;
+    }
+    if (kern == AWQ_GEMV_KERNEL_ROWS) return awq_gemv_rows_supports(M, K, N, g) ? GemvPlan{(int)kern, M} : no_kernel;
+    if (kern == AWQ_GEMV_KERNEL_LDS) return awq_gemv_lds_supports(M, K, N, g) ? GemvPlan{(int)kern, M} : no_kernel;
+    return awq_gemv_nk_supports(M, K, N, g) ? GemvPlan{(int)AWQ_GEMV_KERNEL_TILE16, M} : no_kernel;
+}
+
+// The dispatch of awq_gemv_fast_forward.  AUTO: the batched kernel (GEMVFast form) where it takes the shape, from five rows -- and
+// below five where ONE pass of eight waves covers K (2048 < K <= 4096): there it is ahead of the 16-row kernel at every M
+// (profiles/r05_sweep_small_batch.txt, M = 1: 5.4 / 9.3 / 9.6 / 15.0 us vs 6.2 / 9.7 / 10.1 / 16.3 at N = 4096 / 11008 / 12288 /
+// 22016), behind it at K = 1024 (fewer waves per tile) and from K = 8192 (two passes).  Every number but 0 and BATCH: the 16-row
+// kernel (gemv_fast.hip, M <= 16: the host wrapper chunks).
+GemvPlan gemv_fast_plan(uint32_t kern, int M, int K, int N, int g) {
+    const int rows = batch_rows(awq_gemv_batch_fast_supports, M, K, N, g);
+    if (kern == AWQ_GEMV_KERNEL_BATCH || (kern == AWQ_GEMV_KERNEL_AUTO && (M >= 5 || (K > 2048 && K <= 4096)) && rows))
+        return rows ? GemvPlan{(int)AWQ_GEMV_KERNEL_BATCH, rows} : no_kernel;
+    return M <= 16 && awq_gemv_fast_supports(M, K, N, g) ? GemvPlan{(int)AWQ_GEMV_KERNEL_TILE16, M} : no_kernel;
+}
+}  // namespace
+
+extern "C" {
+
+// Which kernel awq_gemv_forward's AUTO dispatch takes (gemv_plan).  -1: no kernel takes the shape.
 int awq_gemv_auto_kernel(int64_t M, int64_t K, int64_t N, int64_t group_size) {
     if (M <= 0 || K <= 0 || N <= 0 || group_size <= 0 || K % group_size || K % 8 || M > INT32_MAX || K > INT32_MAX || N > INT32_MAX) return -1;
-    const int m = (int)M, k = (int)K, n = (int)N, g = (int)group_size;
-    // round 5: from five rows the batched kernel (gemv_batch.hip: activations in registers, the K range split over the waves of a
-    // block, weights by LDS-DMA) -- up to 32 rows per launch, any M in one call (balanced chunks); it replaces gemv_lds / gemv_nk
-    // wherever it takes the shape (group_size 128): 4096 x 11008, M = 8: see profiles/r05_*; AWQ_GEMV_KERNEL_PREFILL is explicit only
-    // ... and already at four rows while K > 2048, at three where the row-streaming kernel is not the choice (K > 6144): it costs the
-    // same at 1 .. 5 rows while gemv_rows / gemv_nk grow by ~1 us per row (profiles/r05_sweep_small_batch.txt, M = 4: 9.1 vs 10.3 us at
-    // 4096 x 11008, 14.4 vs 15.3 at 4096 x 22016, 12.7 vs 17.6 at 8192 x 7168; level at K = 11008; behind at K = 1024)
-    if ((M >= 5 || (M == 4 && K > 2048) || (M == 3 && K > 6144)) && awq_gemv_batch_supports((int)(M > 32 ? 32 : M), k, n, g))
-        return (int)AWQ_GEMV_KERNEL_BATCH;
-    if (M > 16) return -1;  // the older decode kernels serve 16 rows per call (the host wrapper chunks)
-    // round 4: batch 2 at every K and batches 3 .. 4 while K <= 6144 also run the row-streaming kernel -- it is ahead of the
-    // 16-row tile kernel there on all four 7B shapes (profiles/r03_gemv_rows_sweep.txt: M = 2 4.65 / 7.05 / 10.77 / 8.57 us vs
-    // 6.18 / 9.96 / 16.65 / 10.73; M = 4 at K = 4096 5.79 / 9.79 / 14.39 vs 6.59 / 10.40 / 18.29; at K = 11008 12.25 vs 11.79)
-    if ((M <= 2 || (M <= 4 && K <= 6144)) && awq_gemv_rows_supports(m, k, n, g)) return (int)AWQ_GEMV_KERNEL_ROWS;
-    if (M >= 5 && N >= 8192 && awq_gemv_lds_supports(m, k, n, g)) return (int)AWQ_GEMV_KERNEL_LDS;
-    return awq_gemv_nk_supports(m, k, n, g) ? (int)AWQ_GEMV_KERNEL_TILE16 : -1;
+    return gemv_plan(AWQ_GEMV_KERNEL_AUTO, (int)M, (int)K, (int)N, (int)group_size).kernel;
 }
 
 int awq_gemv_batch_plan(int64_t M, int64_t K, int64_t N, int64_t group_size, int32_t form, int32_t depth, int32_t fast, int32_t* out) {
@@ -430,171 +524,109 @@ int awq_gemv_batch_plan(int64_t M, int64_t K, int64_t N, int64_t group_size, int
 int awq_gemv_forward(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
                      uint16_t* y, int64_t M, int64_t K, int64_t N, int64_t group_size, int64_t zeros_width,
                      uint32_t flags, void* stream) {
-    if (K <= 0 || N < 0 || group_size <= 0 || K % group_size || K % 8 || zeros_width <= 0) return AWQ_ERR_BAD_SHAPE;
-    if (zeros_width * 8 < K / group_size) return AWQ_ERR_BAD_SHAPE;
-    if (M < 0 || M > INT32_MAX || K > INT32_MAX || N > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (M == 0 || N == 0) return AWQ_OK;
-    if (!x || !qweight || !scales || !qzeros || !y) return AWQ_ERR_NULL;
-    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales)) return AWQ_ERR_BAD_ALIGNMENT;
     const uint32_t kern = AWQ_GEMM_FLAG_KERNEL(flags);
-    if (kern == AWQ_GEMV_KERNEL_PREFILL) {
-        if (!aligned16(y)) return AWQ_ERR_BAD_ALIGNMENT;
-        g_last_kernel = "gemm_regb_nk";
-        return awq_launch_gemm_regb_nk(x, qweight, scales, qzeros, nullptr, y, (int)M, (int)K, (int)N, (int)group_size, (int)zeros_width,
-                                       AWQ_GEMM_FLAG_NLOG(flags) == 2 ? 256 : 0, static_cast<hipStream_t>(stream));
-    }
-    const int auto_k = kern == AWQ_GEMV_KERNEL_AUTO ? awq_gemv_auto_kernel(M, K, N, group_size) : -1;
-    if (kern == AWQ_GEMV_KERNEL_BATCH || auto_k == (int)AWQ_GEMV_KERNEL_BATCH) {
-        // one launch per <= 128 rows (round 6: up to four row parts of <= 32 rows, each in its own block, the blocks of a tile list
-        // residents of one XCD so that the matrix is fetched from HBM once); where the parts do not fit the LDS budget (very long
-        // tile lists per block) launches of fewer rows
-        int64_t cap = 128;
-        while (cap > 32 && !awq_gemv_batch_supports((int)(M > cap ? cap : M), (int)K, (int)N, (int)group_size)) cap /= 2;
-        if (!awq_gemv_batch_supports((int)(M > cap ? cap : M), (int)K, (int)N, (int)group_size)) return AWQ_ERR_UNSUPPORTED;
-        g_last_kernel = "gemv_batch";
-        // the tuning bits are the batch kernel's only when the caller picked it: AUTO plans with 0 (flags written for another kernel
-        // must not move the batch kernel's row parts / form / ring depth)
-        const bool tuned = kern == AWQ_GEMV_KERNEL_BATCH;
-        const int form = tuned ? (int)(AWQ_GEMM_FLAG_UNIT(flags) | (AWQ_GEMM_FLAG_WAVES(flags) << 4)) : 0;
-        const int depth = tuned ? (int)AWQ_GEMM_FLAG_SPLITK(flags) : 0;
-        const int64_t nchunk = (M + cap - 1) / cap, rows = (M + nchunk - 1) / nchunk;  // balanced chunks of at most `cap` rows
-        for (int64_t m0 = 0; m0 < M; m0 += rows) {
-            const int mm = (int)(M - m0 < rows ? M - m0 : rows);
-            const int rc = awq_launch_gemv_batch(x + m0 * K, qweight, scales, qzeros, y + m0 * N, mm, (int)K, (int)N, (int)group_size,
-                                                 (int)zeros_width, form, depth, static_cast<hipStream_t>(stream));
-            if (rc != AWQ_OK) return rc;
+    AwqGemvArgs a;
+    const int rc = check_gemv(&a, x, qweight, scales, qzeros, y, M, K, N, group_size, zeros_width, stream, true,
+                              kern != AWQ_GEMV_KERNEL_PREFILL || aligned16(y));
+    if (rc || empty(a)) return rc;
+    const GemvPlan plan = gemv_plan(kern, a.M, a.K, a.N, a.g);
+    const int waves = (int)AWQ_GEMM_FLAG_WAVES(flags), unit = (int)AWQ_GEMM_FLAG_UNIT(flags), split = (int)AWQ_GEMM_FLAG_SPLITK(flags);
+    switch (plan.kernel) {
+        case AWQ_GEMV_KERNEL_PREFILL:
+            g_last_kernel = "gemm_regb_nk";
+            return awq_launch_gemm_regb_nk(a, AWQ_GEMM_FLAG_NLOG(flags) == 2 ? 256 : 0);
+        case AWQ_GEMV_KERNEL_BATCH: {
+            g_last_kernel = "gemv_batch";
+            // the tuning bits are the batch kernel's only when the caller picked it: AUTO plans with 0 (flags written for another kernel
+            // must not move the batch kernel's row parts / form / ring depth)
+            const bool tuned = kern == AWQ_GEMV_KERNEL_BATCH;
+            const int form = tuned ? unit | (waves << 4) : 0, depth = tuned ? split : 0;
+            return launch_row_chunks(a, plan.rows, [&](const AwqGemvArgs& c) { return awq_launch_gemv_batch(c, form, depth); });
         }
-        return AWQ_OK;
+        case AWQ_GEMV_KERNEL_ROWS:
+            g_last_kernel = "gemv_rows";
+            return awq_launch_gemv_rows(a, waves, unit, split, (int)AWQ_GEMM_FLAG_NLOG(flags));
+        case AWQ_GEMV_KERNEL_LDS:
+            g_last_kernel = "gemv_lds";
+            return awq_launch_gemv_lds(a, split, unit);
+        case AWQ_GEMV_KERNEL_TILE16:
+            g_last_kernel = "gemv_nk";
+            return awq_launch_gemv_nk(a, waves, unit);
+        default:
+            return AWQ_ERR_UNSUPPORTED;
     }
-    if (M > 16) return AWQ_ERR_UNSUPPORTED;  // the older decode kernels take at most 16 rows per call
-    if ((kern == AWQ_GEMV_KERNEL_ROWS && awq_gemv_rows_supports((int)M, (int)K, (int)N, (int)group_size)) ||
-        auto_k == (int)AWQ_GEMV_KERNEL_ROWS) {
-        g_last_kernel = "gemv_rows";
-        return awq_launch_gemv_rows(x, qweight, scales, qzeros, y, (int)M, (int)K, (int)N, (int)group_size, (int)zeros_width,
-                                    (int)AWQ_GEMM_FLAG_WAVES(flags), (int)AWQ_GEMM_FLAG_UNIT(flags),
-                                    (int)AWQ_GEMM_FLAG_SPLITK(flags), (int)AWQ_GEMM_FLAG_NLOG(flags),
-                                    static_cast<hipStream_t>(stream));
-    }
-    if (kern == AWQ_GEMV_KERNEL_ROWS) return AWQ_ERR_UNSUPPORTED;
-    if ((kern == AWQ_GEMV_KERNEL_LDS && awq_gemv_lds_supports((int)M, (int)K, (int)N, (int)group_size)) ||
-        auto_k == (int)AWQ_GEMV_KERNEL_LDS) {
-        g_last_kernel = "gemv_lds";
-        return awq_launch_gemv_lds(x, qweight, scales, qzeros, y, (int)M, (int)K, (int)N, (int)group_size, (int)zeros_width,
-                                   (int)AWQ_GEMM_FLAG_SPLITK(flags), (int)AWQ_GEMM_FLAG_UNIT(flags), static_cast<hipStream_t>(stream));
-    }
-    if (kern == AWQ_GEMV_KERNEL_LDS) return AWQ_ERR_UNSUPPORTED;
-    if (!awq_gemv_nk_supports((int)M, (int)K, (int)N, (int)group_size)) return AWQ_ERR_UNSUPPORTED;
-    g_last_kernel = "gemv_nk";
-    return awq_launch_gemv_nk(x, qweight, scales, qzeros, y, (int)M, (int)K, (int)N, (int)group_size, (int)zeros_width,
-                              (int)AWQ_GEMM_FLAG_WAVES(flags), (int)AWQ_GEMM_FLAG_UNIT(flags),
-                              static_cast<hipStream_t>(stream));
 }
 
 int awq_gemv_forward_ex(const AwqGemvEx* e) {
-    if (!e || e->struct_bytes != sizeof(AwqGemvEx)) return AWQ_ERR_BAD_SHAPE;
-    const int64_t M = e->M, K = e->K, N = e->N, g = e->group_size, ZW = e->zeros_width;
-    if (K <= 0 || N < 0 || g <= 0 || K % g || K % 8 || ZW <= 0 || ZW * 8 < K / g) return AWQ_ERR_BAD_SHAPE;
-    if (M < 0 || M > INT32_MAX || K > INT32_MAX || N > INT32_MAX || (e->flags & ~AWQ_GEMV_EX_SILU_PAIRS)) return AWQ_ERR_BAD_SHAPE;
+    if (!e || e->struct_bytes != sizeof(AwqGemvEx)) return AWQ_ERR_BAD_SHAPE;  // (a NULL struct too: as published)
     const bool pairs = e->flags & AWQ_GEMV_EX_SILU_PAIRS;
-    if (pairs && (e->add_residual || N % 2)) return AWQ_ERR_BAD_SHAPE;
-    if (M == 0 || N == 0) return AWQ_OK;
-    if (!e->x || !e->qweight || !e->scales || !e->qzeros || !e->y) return AWQ_ERR_NULL;
-    if (!aligned16(e->x) || !aligned16(e->qweight) || !aligned16(e->scales) || (e->norm_weight && !aligned16(e->norm_weight)))
-        return AWQ_ERR_BAD_ALIGNMENT;
-    if (M != 1) return AWQ_ERR_UNSUPPORTED;
+    if ((e->flags & ~AWQ_GEMV_EX_SILU_PAIRS) || (pairs && (e->add_residual || e->N % 2))) return AWQ_ERR_BAD_SHAPE;
+    AwqGemvArgs a;
+    const int rc = check_gemv(&a, e->x, e->qweight, e->scales, e->qzeros, e->y, e->M, e->K, e->N, e->group_size, e->zeros_width,
+                              e->stream, true, !e->norm_weight || aligned16(e->norm_weight));
+    if (rc || empty(a)) return rc;
+    if (a.M != 1) return AWQ_ERR_UNSUPPORTED;
     const AwqRowsFx fx{e->norm_weight, e->norm_eps, e->add_residual, pairs};
     g_last_kernel = "gemv_rows";
-    return awq_launch_gemv_rows(e->x, e->qweight, e->scales, e->qzeros, e->y, (int)M, (int)K, (int)N, (int)g, (int)ZW, 0, 0, 0, 0,
-                                static_cast<hipStream_t>(e->stream), &fx);
+    return awq_launch_gemv_rows(a, 0, 0, 0, 0, &fx);
 }
 
 int awq_grouped_gemv_forward(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
                              uint16_t* y, const int32_t* pair_experts, const float* pair_weights, int64_t num_pairs,
                              int64_t x_div, int64_t num_experts, int64_t first_expert, int64_t K, int64_t N, int64_t group_size,
                              int64_t zeros_width, uint32_t flags, int64_t parts, void* stream) {
-    const int64_t g = group_size, ZW = zeros_width;
     if (first_expert < 0 || first_expert > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (K <= 0 || N < 0 || g <= 0 || K % g || K % 8 || ZW <= 0 || ZW * 8 < K / g) return AWQ_ERR_BAD_SHAPE;
-    if (num_pairs < 0 || num_experts < 1 || x_div < 1 || parts < 0 || K > INT32_MAX || N > INT32_MAX || num_experts > INT32_MAX ||
-        (flags & ~AWQ_GEMV_EX_SILU_PAIRS))
+    if (num_pairs < 0 || num_experts < 1 || num_experts > INT32_MAX || x_div < 1 || parts < 0 || (flags & ~AWQ_GEMV_EX_SILU_PAIRS))
         return AWQ_ERR_BAD_SHAPE;
     const bool pairs = flags & AWQ_GEMV_EX_SILU_PAIRS;
     if (pairs && (pair_weights || N % 2)) return AWQ_ERR_BAD_SHAPE;
-    if (num_pairs == 0 || N == 0) return AWQ_OK;
-    if (!x || !qweight || !scales || !qzeros || !y || !pair_experts) return AWQ_ERR_NULL;
-    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales)) return AWQ_ERR_BAD_ALIGNMENT;
+    AwqGemvArgs a;
+    // one virtual batch-1 call per pair (a count past the limit is refused below, not by the range of M)
+    const int rc = check_gemv(&a, x, qweight, scales, qzeros, y, num_pairs ? 1 : 0, K, N, group_size, zeros_width, stream, pair_experts != nullptr);
+    if (rc || empty(a)) return rc;
+    // (the limits come after the pointer and alignment checks: as published)
     if (num_pairs > 8191 || parts > 65535 || x_div > num_pairs) return AWQ_ERR_UNSUPPORTED;
     // the per-expert strides must keep every expert's tensors 16-byte aligned (whole rows of 16-byte multiples)
-    if ((N * (K / 8) * 4) % 16 || (N * ZW * 16) % 16) return AWQ_ERR_UNSUPPORTED;
+    if ((N * (K / 8) * 4) % 16 || (N * zeros_width * 16) % 16) return AWQ_ERR_UNSUPPORTED;
     AwqRowsFx fx;
-    fx.pairs = pairs;
-    fx.pair_expert = pair_experts;
-    fx.pair_scale = pair_weights;
-    fx.num_pairs = (int)num_pairs;
-    fx.num_experts = (int)num_experts;
-    fx.first_expert = (int)first_expert;
-    fx.x_div = (int)x_div;
-    fx.parts = (int)parts;
+    fx.pairs = pairs; fx.pair_expert = pair_experts; fx.pair_scale = pair_weights;
+    fx.num_pairs = (int)num_pairs; fx.num_experts = (int)num_experts; fx.first_expert = (int)first_expert;
+    fx.x_div = (int)x_div; fx.parts = (int)parts;
     g_last_kernel = "gemv_rows_grouped";
-    return awq_launch_gemv_rows(x, qweight, scales, qzeros, y, 1, (int)K, (int)N, (int)g, (int)ZW, 0, 0, 0, 0,
-                                static_cast<hipStream_t>(stream), &fx);
+    return awq_launch_gemv_rows(a, 0, 0, 0, 0, &fx);
 }
 
 size_t awq_gemv_lds_bytes(int64_t M, int64_t K, int64_t zeros_width) {
     return awq_gemv_nk_lds_bytes((int)M, (int)K, (int)zeros_width, 8);
 }
 
+// (the two dequantisers have looser shape rules than the forward entries -- no range, no width -- and check less alignment: as published)
 int awq_dequantize_weights_gemv(const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* out,
                                 int64_t K, int64_t N, int64_t group_size, int64_t zeros_width, void* stream) {
     if (K < 0 || N < 0 || group_size <= 0 || K % 8 || group_size % 8 || (K && K % group_size)) return AWQ_ERR_BAD_SHAPE;
     if (K * N == 0) return AWQ_OK;
     if (!qweight || !scales || !qzeros || !out) return AWQ_ERR_NULL;
     if (!aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
-    return awq_launch_dequant_nk(qweight, scales, qzeros, out, (int)K, (int)N, (int)group_size, (int)zeros_width,
-                                 static_cast<hipStream_t>(stream));
+    return awq_launch_dequant_nk(gemv_args(nullptr, qweight, scales, qzeros, out, 0, K, N, group_size, zeros_width, stream));
 }
-
-/* ---- GEMVFast layout --------------------------------------------------------------------- */
 
 int awq_gemv_fast_forward(const uint16_t* x, const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros,
                           uint16_t* y, int64_t M, int64_t K, int64_t N, int64_t group_size, int64_t group_rows,
                           uint32_t flags, void* stream) {
-    if (K <= 0 || N < 0 || group_size <= 0 || K % group_size || N % 4 || K % 64) return AWQ_ERR_BAD_SHAPE;
-    if (group_rows < K / group_size) return AWQ_ERR_BAD_SHAPE;
-    if (M < 0 || M > INT32_MAX || K > INT32_MAX || N > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (M == 0 || N == 0) return AWQ_OK;
-    if (!x || !qweight || !scales || !qzeros || !y) return AWQ_ERR_NULL;
-    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales) || !aligned16(qzeros)) return AWQ_ERR_BAD_ALIGNMENT;
-    // round 5: from five rows the batched kernel (gemv_batch.hip, GEMVFast form: any M in launches of <= 32 rows); AWQ_GEMM_FLAG_KERNEL:
-    // 0 = auto, 1 = the 16-row kernel (gemv_fast.hip, M <= 16), AWQ_GEMV_KERNEL_BATCH = the batched kernel
+    AwqGemvArgs a;
+    const int rc = check_gemv_fast(&a, x, qweight, scales, qzeros, y, M, K, N, group_size, group_rows, stream);
+    if (rc || empty(a)) return rc;
     const uint32_t kern = AWQ_GEMM_FLAG_KERNEL(flags);
-    int64_t fcap = 128;  // rows per launch (round 6: row parts across blocks, see gemv_batch.hip)
-    while (fcap > 32 && !awq_gemv_batch_fast_supports((int)(M > fcap ? fcap : M), (int)K, (int)N, (int)group_size)) fcap /= 2;
-    const bool batch_ok = awq_gemv_batch_fast_supports((int)(M > fcap ? fcap : M), (int)K, (int)N, (int)group_size);
-    // below five rows AUTO takes it where ONE pass of eight waves covers K (2048 < K <= 4096): there it is ahead of the 16-row kernel at
-    // every M (profiles/r05_sweep_small_batch.txt, M = 1: 5.4 / 9.3 / 9.6 / 15.0 us vs 6.2 / 9.7 / 10.1 / 16.3 at N = 4096 / 11008 /
-    // 12288 / 22016), behind it at K = 1024 (fewer waves per tile) and from K = 8192 (two passes)
-    const bool small_ok = K > 2048 && K <= 4096;
-    if (kern == AWQ_GEMV_KERNEL_BATCH || (kern == 0 && (M >= 5 || small_ok) && batch_ok)) {
-        if (!batch_ok) return AWQ_ERR_UNSUPPORTED;
+    const GemvPlan plan = gemv_fast_plan(kern, a.M, a.K, a.N, a.g);
+    if (plan.kernel == (int)AWQ_GEMV_KERNEL_BATCH) {
         g_last_kernel = "gemv_batch_fast";
         // (tuning bits only when the caller picked the batch kernel: AUTO plans with 0)
         const int depth = kern == AWQ_GEMV_KERNEL_BATCH ? (int)((AWQ_GEMM_FLAG_SPLITK(flags) & 15u) | (AWQ_GEMM_FLAG_WAVES(flags) << 4)) : 0;
-        const int64_t nchunk = (M + fcap - 1) / fcap, rows = (M + nchunk - 1) / nchunk;
-        for (int64_t m0 = 0; m0 < M; m0 += rows) {
-            const int mm = (int)(M - m0 < rows ? M - m0 : rows);
-            const int rc = awq_launch_gemv_batch_fast(x + m0 * K, qweight, scales, qzeros, y + m0 * N, mm, (int)K, (int)N, (int)group_size,
-                                                      (int)group_rows, depth, static_cast<hipStream_t>(stream));
-            if (rc != AWQ_OK) return rc;
-        }
-        return AWQ_OK;
+        return launch_row_chunks(a, plan.rows, [&](const AwqGemvArgs& c) { return awq_launch_gemv_batch_fast(c, depth); });
     }
-    if (M > 16) return AWQ_ERR_UNSUPPORTED;  // the 16-row kernel (the host wrapper chunks)
-    if (!awq_gemv_fast_supports((int)M, (int)K, (int)N, (int)group_size)) return AWQ_ERR_UNSUPPORTED;
+    if (plan.kernel < 0) return AWQ_ERR_UNSUPPORTED;
     g_last_kernel = "gemv_fast";
-    return awq_launch_gemv_fast(x, qweight, scales, qzeros, y, (int)M, (int)K, (int)N, (int)group_size, (int)group_rows,
-                                (int)AWQ_GEMM_FLAG_WAVES(flags), (int)AWQ_GEMM_FLAG_UNIT(flags),
-                                static_cast<hipStream_t>(stream));
+    return awq_launch_gemv_fast(a, (int)AWQ_GEMM_FLAG_WAVES(flags), (int)AWQ_GEMM_FLAG_UNIT(flags));
 }
 
 // Prefill-sized batches on the GEMVFast layout: the packed words are transposed into the caller's temporary (repack.hip), then the
@@ -602,19 +634,16 @@ int awq_gemv_fast_forward(const uint16_t* x, const int16_t* qweight, const uint1
 int awq_gemv_fast_prefill(const uint16_t* x, const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros, uint16_t* y,
                           int32_t* qweight_tmp, int64_t M, int64_t K, int64_t N, int64_t group_size, int64_t group_rows, uint32_t flags,
                           void* stream) {
-    if (K <= 0 || N < 0 || group_size <= 0 || K % group_size || N % 4 || K % 64) return AWQ_ERR_BAD_SHAPE;
-    if (group_rows < K / group_size) return AWQ_ERR_BAD_SHAPE;
-    if (M < 0 || M > INT32_MAX || K > INT32_MAX || N > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (M == 0 || N == 0) return AWQ_OK;
-    if (!x || !qweight || !scales || !qzeros || !y || !qweight_tmp) return AWQ_ERR_NULL;
-    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales) || !aligned16(qzeros) || !aligned16(y) || !aligned16(qweight_tmp))
-        return AWQ_ERR_BAD_ALIGNMENT;
-    if (N % 8 || !awq_gemm_regb_supports((int)M, (int)K, (int)N, (int)group_size)) return AWQ_ERR_UNSUPPORTED;
-    int rc = awq_repack_gemvfast_to_gemm(qweight, qweight_tmp, K, N, stream);
+    AwqGemvArgs a;
+    int rc = check_gemv_fast(&a, x, qweight, scales, qzeros, y, M, K, N, group_size, group_rows, stream, qweight_tmp != nullptr,
+                             aligned16(y) && aligned16(qweight_tmp));
+    if (rc || empty(a)) return rc;
+    if (N % 8 || !awq_gemm_regb_supports(a.M, a.K, a.N, a.g)) return AWQ_ERR_UNSUPPORTED;
+    rc = awq_repack_gemvfast_to_gemm(qweight, qweight_tmp, K, N, stream);
     if (rc != AWQ_OK) return rc;
     g_last_kernel = "repack_fast+gemm_regb_fz";
-    return awq_launch_gemm_regb_fz(x, qweight_tmp, scales, qzeros, y, (int)M, (int)K, (int)N, (int)group_size,
-                                   AWQ_GEMM_FLAG_NLOG(flags) == 2 ? 256 : 0, static_cast<hipStream_t>(stream));
+    a.qweight = qweight_tmp;  // the GEMM runs on the transposed words
+    return awq_launch_gemm_regb_fz(a, AWQ_GEMM_FLAG_NLOG(flags) == 2 ? 256 : 0);
 }
 
 size_t awq_gemv_fast_lds_bytes_c(int64_t M, int64_t K, int64_t group_size) {
@@ -626,8 +655,7 @@ int awq_dequantize_weights_gemv_fast(const int16_t* qweight, const uint16_t* sca
     if (K < 0 || N < 0 || group_size <= 0 || K % 64 || N % 4 || (K && K % group_size)) return AWQ_ERR_BAD_SHAPE;
     if (K * N == 0) return AWQ_OK;
     if (!qweight || !scales || !qzeros || !out) return AWQ_ERR_NULL;
-    return awq_launch_dequant_fast(qweight, scales, qzeros, out, (int)K, (int)N, (int)group_size,
-                                   static_cast<hipStream_t>(stream));
+    return awq_launch_dequant_fast(gemv_args(nullptr, qweight, scales, qzeros, out, 0, K, N, group_size, 0, stream));
 }
 
 }  // extern "C"

@@ -610,18 +610,18 @@ int awq_launch_gemm_regb(const AwqGemmArgs& a, int bm) {
 }
 
 // ---- the FZ form: GEMM-layout words (a repacked temporary) with the GEMVFast format's scales / fp16 zero terms [>= K/g, N]
-int awq_launch_gemm_regb_fz(const uint16_t* x, const int32_t* qweight_kn, const uint16_t* scales, const uint16_t* qzeros_f16, uint16_t* y,
-                            int M, int K, int N, int g, int bm, hipStream_t st) {
+int awq_launch_gemm_regb_fz(const AwqGemvArgs& a, int bm) {
+    const int M = a.M, K = a.K, N = a.N, g = a.g;
     if (!awq_gemm_regb_supports(M, K, N, g)) return AWQ_ERR_UNSUPPORTED;
     if (bm == 0) bm = 128;
     if (bm != 128 && bm != 256) return AWQ_ERR_UNSUPPORTED;
     RegbParams p;
-    p.qweight = reinterpret_cast<const uint32_t*>(qweight_kn);
-    p.qzeros = reinterpret_cast<const uint32_t*>(qzeros_f16);
-    p.scales = reinterpret_cast<const half_t*>(scales);
-    p.x = reinterpret_cast<const half_t*>(x);
+    p.qweight = static_cast<const uint32_t*>(a.qweight);
+    p.qzeros = static_cast<const uint32_t*>(a.qzeros);
+    p.scales = reinterpret_cast<const half_t*>(a.scales);
+    p.x = reinterpret_cast<const half_t*>(a.x);
     p.bias = nullptr;
-    p.y = reinterpret_cast<half_t*>(y);
+    p.y = reinterpret_cast<half_t*>(a.y);
     p.M = M; p.K = K; p.N = N; p.g = g;
     p.KW = p.ZW = p.SW = 0;
     p.seg = nullptr; p.E = 0; p.w_stride = p.z_stride = p.s_stride = 0;
@@ -636,9 +636,9 @@ int awq_launch_gemm_regb_fz(const uint16_t* x, const int32_t* qweight_kn, const 
     if (bm == 256) {
         static std::atomic<unsigned long long> opted{0};
         if (!awq_lds_opt_in(reinterpret_cast<const void*>(&awq_gemm_regb_kernel<2, 0, false, false, true>), opted)) return AWQ_ERR_LAUNCH;
-        hipLaunchKernelGGL((awq_gemm_regb_kernel<2, 0, false, false, true>), dim3(grid), dim3(512), lds, st, p);
+        hipLaunchKernelGGL((awq_gemm_regb_kernel<2, 0, false, false, true>), dim3(grid), dim3(512), lds, a.stream, p);
     } else {
-        hipLaunchKernelGGL((awq_gemm_regb_kernel<1, 0, false, false, true>), dim3(grid), dim3(256), lds, st, p);
+        hipLaunchKernelGGL((awq_gemm_regb_kernel<1, 0, false, false, true>), dim3(grid), dim3(256), lds, a.stream, p);
     }
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
@@ -650,18 +650,18 @@ bool awq_gemm_regb_nk_supports(int M, int K, int N, int g, int ZW) {
            (int64_t)N * ZW * 16 < ((int64_t)1 << 31);
 }
 
-int awq_launch_gemm_regb_nk(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
-                            const uint16_t* bias, uint16_t* y, int M, int K, int N, int g, int ZW, int bm, hipStream_t st) {
+int awq_launch_gemm_regb_nk(const AwqGemvArgs& a, int bm) {
+    const int M = a.M, K = a.K, N = a.N, g = a.g, ZW = a.width;
     if (!awq_gemm_regb_nk_supports(M, K, N, g, ZW)) return AWQ_ERR_UNSUPPORTED;
     if (bm == 0) bm = 128;
     if (bm != 128 && bm != 256) return AWQ_ERR_UNSUPPORTED;
     RegbParams p;
-    p.qweight = reinterpret_cast<const uint32_t*>(qweight);
-    p.qzeros = reinterpret_cast<const uint32_t*>(qzeros);
-    p.scales = reinterpret_cast<const half_t*>(scales);
-    p.x = reinterpret_cast<const half_t*>(x);
-    p.bias = reinterpret_cast<const half_t*>(bias);
-    p.y = reinterpret_cast<half_t*>(y);
+    p.qweight = static_cast<const uint32_t*>(a.qweight);
+    p.qzeros = static_cast<const uint32_t*>(a.qzeros);
+    p.scales = reinterpret_cast<const half_t*>(a.scales);
+    p.x = reinterpret_cast<const half_t*>(a.x);
+    p.bias = nullptr;  // (no entry point of this layout takes one)
+    p.y = reinterpret_cast<half_t*>(a.y);
     p.M = M; p.K = K; p.N = N; p.g = g;
     p.KW = K / 8; p.ZW = ZW; p.SW = 8 * ZW;
     p.seg = nullptr; p.E = 0; p.w_stride = p.z_stride = p.s_stride = 0;
@@ -676,9 +676,9 @@ int awq_launch_gemm_regb_nk(const uint16_t* x, const int32_t* qweight, const uin
     if (bm == 256) {
         static std::atomic<unsigned long long> opted{0};
         if (!awq_lds_opt_in(reinterpret_cast<const void*>(&awq_gemm_regb_kernel<2, 0, true>), opted)) return AWQ_ERR_LAUNCH;
-        hipLaunchKernelGGL((awq_gemm_regb_kernel<2, 0, true>), dim3(grid), dim3(512), lds, st, p);
+        hipLaunchKernelGGL((awq_gemm_regb_kernel<2, 0, true>), dim3(grid), dim3(512), lds, a.stream, p);
     } else {
-        hipLaunchKernelGGL((awq_gemm_regb_kernel<1, 0, true>), dim3(grid), dim3(256), lds, st, p);
+        hipLaunchKernelGGL((awq_gemm_regb_kernel<1, 0, true>), dim3(grid), dim3(256), lds, a.stream, p);
     }
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }

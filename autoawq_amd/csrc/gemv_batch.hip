@@ -710,10 +710,9 @@ int launch_batch(const void* x, const void* qweight, const void* scales, const v
 
 // form: how the activations reach the registers (0 = auto, 1 = LDS staging area, 2 = direct fragment loads); depth: ring slots per wave
 // (1 | 3: that many pieces in flight; 2: the next piece is requested when a piece lands; 0 = auto)
-int awq_launch_gemv_batch(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* y,
-                          int M, int K, int N, int g, int ZW, int form, int depth, hipStream_t st) {
-    if (ZW * 8 < K / 128) return AWQ_ERR_BAD_SHAPE;
-    return launch_batch(x, qweight, scales, qzeros, y, M, K, N, g, ZW, 0, form, depth, false, st);
+int awq_launch_gemv_batch(const AwqGemvArgs& a, int form, int depth) {
+    if (a.width * 8 < a.K / 128) return AWQ_ERR_BAD_SHAPE;
+    return launch_batch(a.x, a.qweight, a.scales, a.qzeros, a.y, a.M, a.K, a.N, a.g, a.width, 0, form, depth, false, a.stream);
 }
 
 bool awq_gemv_batch_fast_supports(int M, int K, int N, int g) {
@@ -733,10 +732,9 @@ bool awq_gemv_batch_plan_fill(int M, int K, int N, int g, int form, int depth, b
 }
 
 // the same kernel on the GEMVFast layout's buffers (qweight int16 [N/4, K], scales / qzeros fp16 [group_rows, N]); depth 1 | 2
-int awq_launch_gemv_batch_fast(const uint16_t* x, const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros, uint16_t* y,
-                               int M, int K, int N, int g, int group_rows, int depth, hipStream_t st) {
-    if (group_rows < K / 128) return AWQ_ERR_BAD_SHAPE;
+int awq_launch_gemv_batch_fast(const AwqGemvArgs& a, int depth) {
+    if (a.width < a.K / 128) return AWQ_ERR_BAD_SHAPE;
     const int parts = (depth >> 4) & 15;  // (row parts across blocks: see plan_batch)
     depth &= 15;
-    return launch_batch(x, qweight, scales, qzeros, y, M, K, N, g, 0, group_rows, parts << 4, depth, true, st);
+    return launch_batch(a.x, a.qweight, a.scales, a.qzeros, a.y, a.M, a.K, a.N, a.g, 0, a.width, parts << 4, depth, true, a.stream);
 }

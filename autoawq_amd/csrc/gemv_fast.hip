@@ -253,8 +253,8 @@ bool awq_gemv_fast_supports(int M, int K, int N, int g) {
     return true;
 }
 
-int awq_launch_gemv_fast(const uint16_t* x, const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros,
-                         uint16_t* y, int M, int K, int N, int g, int GP, int nwaves, int unroll, hipStream_t st) {
+int awq_launch_gemv_fast(const AwqGemvArgs& a, int nwaves, int unroll) {
+    const int M = a.M, K = a.K, N = a.N, g = a.g, GP = a.width;
     if (!awq_gemv_fast_supports(M, K, N, g)) return AWQ_ERR_UNSUPPORTED;
     if (GP < K / g) return AWQ_ERR_BAD_SHAPE;
     const int iters = K / 128;
@@ -263,34 +263,34 @@ int awq_launch_gemv_fast(const uint16_t* x, const int16_t* qweight, const uint16
     const size_t lds = awq_gemv_fast_lds_bytes(M, K, g, nwaves);
     if (lds > 160 * 1024) return AWQ_ERR_UNSUPPORTED;  // caller chunks M
     GemvFastParams p;
-    p.qweight = reinterpret_cast<const uint32_t*>(qweight);
-    p.qzeros = reinterpret_cast<const half_t*>(qzeros);
-    p.scales = reinterpret_cast<const half_t*>(scales);
-    p.x = reinterpret_cast<const half_t*>(x);
-    p.y = reinterpret_cast<half_t*>(y);
+    p.qweight = static_cast<const uint32_t*>(a.qweight);
+    p.qzeros = static_cast<const half_t*>(a.qzeros);
+    p.scales = reinterpret_cast<const half_t*>(a.scales);
+    p.x = reinterpret_cast<const half_t*>(a.x);
+    p.y = reinterpret_cast<half_t*>(a.y);
     p.M = M; p.K = K; p.N = N; p.g = g;
     p.GP = GP;
     p.xpitch = K + 8;
     if (!awq_magic_u32((uint32_t)g, (uint32_t)K + 128u, &p.g_magic) || !awq_magic_u32((uint32_t)(K / 32), 17u * (uint32_t)(K / 32) + 1u, &p.xb_magic))
         return AWQ_ERR_UNSUPPORTED;
-    if (nwaves == 4 && unroll == 4) launch_fast<4, 4>(p, lds, st);
-    else if (nwaves == 4 && unroll == 8) launch_fast<4, 8>(p, lds, st);
-    else if (nwaves == 8 && unroll == 4) launch_fast<8, 4>(p, lds, st);
-    else if (nwaves == 8 && unroll == 8) launch_fast<8, 8>(p, lds, st);
-    else if (nwaves == 16 && unroll == 4) launch_fast<16, 4>(p, lds, st);
+    if (nwaves == 4 && unroll == 4) launch_fast<4, 4>(p, lds, a.stream);
+    else if (nwaves == 4 && unroll == 8) launch_fast<4, 8>(p, lds, a.stream);
+    else if (nwaves == 8 && unroll == 4) launch_fast<8, 4>(p, lds, a.stream);
+    else if (nwaves == 8 && unroll == 8) launch_fast<8, 8>(p, lds, a.stream);
+    else if (nwaves == 16 && unroll == 4) launch_fast<16, 4>(p, lds, a.stream);
     else return AWQ_ERR_UNSUPPORTED;
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
 
-int awq_launch_dequant_fast(const int16_t* qweight, const uint16_t* scales, const uint16_t* qzeros, uint16_t* out, int K,
-                            int N, int g, hipStream_t st) {
+int awq_launch_dequant_fast(const AwqGemvArgs& a) {
+    const int K = a.K, N = a.N, g = a.g;
     if (K % 64 || N % 4 || g <= 0 || K % g) return AWQ_ERR_BAD_SHAPE;
     const int64_t total = (int64_t)(N / 4) * (K / 2);
     if (total == 0) return AWQ_OK;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(awq_dequant_fast_kernel, dim3((unsigned)blocks), dim3(256), 0, st,
-                       reinterpret_cast<const uint32_t*>(qweight), reinterpret_cast<const half_t*>(qzeros),
-                       reinterpret_cast<const half_t*>(scales), reinterpret_cast<half_t*>(out), N, K, g);
+    hipLaunchKernelGGL(awq_dequant_fast_kernel, dim3((unsigned)blocks), dim3(256), 0, a.stream,
+                       static_cast<const uint32_t*>(a.qweight), static_cast<const half_t*>(a.qzeros),
+                       reinterpret_cast<const half_t*>(a.scales), reinterpret_cast<half_t*>(a.y), N, K, g);
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }

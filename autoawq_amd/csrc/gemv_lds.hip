@@ -253,16 +253,16 @@ bool awq_gemv_lds_supports(int M, int K, int N, int g) {
     return xf + 2 * cg + 8 * PIECE_B + 8 * 1024 <= 160 * 1024;  // eight waves, one piece in flight and one tile buffer each, at least
 }
 
-int awq_launch_gemv_lds(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* y,
-                        int M, int K, int N, int g, int ZW, int ks, int depth, hipStream_t st) {
+int awq_launch_gemv_lds(const AwqGemvArgs& a, int ks, int depth) {
+    const int M = a.M, K = a.K, N = a.N, g = a.g, ZW = a.width;
     if (!awq_gemv_lds_supports(M, K, N, g)) return AWQ_ERR_UNSUPPORTED;
     if (ZW * 8 < K / 128) return AWQ_ERR_BAD_SHAPE;
     LdsParams p;
-    p.qweight = reinterpret_cast<const uint32_t*>(qweight);
-    p.qzeros = reinterpret_cast<const uint32_t*>(qzeros);
-    p.scales = reinterpret_cast<const half_t*>(scales);
-    p.x = reinterpret_cast<const half_t*>(x);
-    p.y = reinterpret_cast<half_t*>(y);
+    p.qweight = static_cast<const uint32_t*>(a.qweight);
+    p.qzeros = static_cast<const uint32_t*>(a.qzeros);
+    p.scales = reinterpret_cast<const half_t*>(a.scales);
+    p.x = reinterpret_cast<const half_t*>(a.x);
+    p.y = reinterpret_cast<half_t*>(a.y);
     p.M = M; p.K = K; p.N = N;
     p.KW = K / 8; p.ZW = ZW; p.SW = 8 * ZW;
     p.npiece = (K + 1023) / 1024;
@@ -293,7 +293,7 @@ int awq_launch_gemv_lds(const uint16_t* x, const int32_t* qweight, const uint16_
     if (NW == NWV && RD == RDV) {                                                                                                      \
         static std::atomic<unsigned long long> opted{0};                                                                               \
         if (!awq_lds_opt_in(reinterpret_cast<const void*>(&awq_gemv_lds_kernel<NWV, RDV>), opted)) return AWQ_ERR_LAUNCH;              \
-        hipLaunchKernelGGL((awq_gemv_lds_kernel<NWV, RDV>), dim3((unsigned)blocks), dim3(NWV * 64), lds, st, p);                       \
+        hipLaunchKernelGGL((awq_gemv_lds_kernel<NWV, RDV>), dim3((unsigned)blocks), dim3(NWV * 64), lds, a.stream, p);                 \
         return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;                                                              \
     }
     AWQ_LDS_CASE(8, 1) AWQ_LDS_CASE(4, 2) AWQ_LDS_CASE(4, 3)

@@ -263,19 +263,19 @@ bool awq_gemv_nk_supports(int M, int K, int N, int g) {
     return true;
 }
 
-int awq_launch_gemv_nk(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
-                       uint16_t* y, int M, int K, int N, int g, int ZW, int nwaves, int unroll, hipStream_t st) {
+int awq_launch_gemv_nk(const AwqGemvArgs& a, int nwaves, int unroll) {
+    const int M = a.M, K = a.K, N = a.N, g = a.g, ZW = a.width;
     if (!awq_gemv_nk_supports(M, K, N, g)) return AWQ_ERR_UNSUPPORTED;
     const int iters = (K + 127) / 128;
     if (nwaves == 0) nwaves = 8;
     if (unroll == 0) unroll = (iters + nwaves - 1) / nwaves > 4 ? 8 : 4;
     if (awq_gemv_nk_lds_bytes(M, K, ZW, nwaves) > 160 * 1024) return AWQ_ERR_UNSUPPORTED;  // caller chunks M
     GemvNkParams p;
-    p.qweight = reinterpret_cast<const uint32_t*>(qweight);
-    p.qzeros = reinterpret_cast<const uint32_t*>(qzeros);
-    p.scales = reinterpret_cast<const half_t*>(scales);
-    p.x = reinterpret_cast<const half_t*>(x);
-    p.y = reinterpret_cast<half_t*>(y);
+    p.qweight = static_cast<const uint32_t*>(a.qweight);
+    p.qzeros = static_cast<const uint32_t*>(a.qzeros);
+    p.scales = reinterpret_cast<const half_t*>(a.scales);
+    p.x = reinterpret_cast<const half_t*>(a.x);
+    p.y = reinterpret_cast<half_t*>(a.y);
     p.M = M; p.K = K; p.N = N; p.g = g;
     p.KW = K / 8; p.ZW = ZW;
     p.xpitch = K + 8;
@@ -284,24 +284,24 @@ int awq_launch_gemv_nk(const uint16_t* x, const int32_t* qweight, const uint16_t
         (ZW > 1 && !awq_magic_u32((uint32_t)ZW, 16u * (uint32_t)ZW + 1u, &p.zw_magic)))
         return AWQ_ERR_UNSUPPORTED;
     const size_t lds = awq_gemv_nk_lds_bytes(M, K, ZW, nwaves);
-    if (nwaves == 4 && unroll == 4) launch_nk<4, 4>(p, lds, st);
-    else if (nwaves == 4 && unroll == 8) launch_nk<4, 8>(p, lds, st);
-    else if (nwaves == 8 && unroll == 4) launch_nk<8, 4>(p, lds, st);
-    else if (nwaves == 8 && unroll == 8) launch_nk<8, 8>(p, lds, st);
-    else if (nwaves == 16 && unroll == 4) launch_nk<16, 4>(p, lds, st);
+    if (nwaves == 4 && unroll == 4) launch_nk<4, 4>(p, lds, a.stream);
+    else if (nwaves == 4 && unroll == 8) launch_nk<4, 8>(p, lds, a.stream);
+    else if (nwaves == 8 && unroll == 4) launch_nk<8, 4>(p, lds, a.stream);
+    else if (nwaves == 8 && unroll == 8) launch_nk<8, 8>(p, lds, a.stream);
+    else if (nwaves == 16 && unroll == 4) launch_nk<16, 4>(p, lds, a.stream);
     else return AWQ_ERR_UNSUPPORTED;
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
 
-int awq_launch_dequant_nk(const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* out, int K,
-                          int N, int g, int ZW, hipStream_t st) {
+int awq_launch_dequant_nk(const AwqGemvArgs& a) {
+    const int K = a.K, N = a.N, g = a.g, ZW = a.width;
     if (K % 8 || g % 8 || N < 0) return AWQ_ERR_BAD_SHAPE;
     const int64_t total = (int64_t)N * (K / 8);
     if (total == 0) return AWQ_OK;
     int64_t blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(awq_dequant_nk_kernel, dim3((unsigned)blocks), dim3(256), 0, st,
-                       reinterpret_cast<const uint32_t*>(qweight), reinterpret_cast<const uint32_t*>(qzeros),
-                       reinterpret_cast<const half_t*>(scales), reinterpret_cast<half_t*>(out), N, K / 8, ZW, g);
+    hipLaunchKernelGGL(awq_dequant_nk_kernel, dim3((unsigned)blocks), dim3(256), 0, a.stream,
+                       static_cast<const uint32_t*>(a.qweight), static_cast<const uint32_t*>(a.qzeros),
+                       reinterpret_cast<const half_t*>(a.scales), reinterpret_cast<half_t*>(a.y), N, K / 8, ZW, g);
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }

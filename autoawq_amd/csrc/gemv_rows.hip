@@ -782,9 +782,8 @@ extern "C" __attribute__((visibility("default"))) void awq_debug_set_trace_rows(
 // fx (decoder-block prologue / epilogue, batch 1 with whole rows per wave, else AWQ_ERR_UNSUPPORTED and the caller runs the
 // separate launches): norm_w != null -> x is RMS-normalised while it is brought into registers; res != null -> y = fp16(fp16(W x)
 // + res); pairs -> rows (2 i, 2 i + 1) are (gate_i, up_i) and y [N / 2] = silu(gate) * up.
-int awq_launch_gemv_rows(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
-                         uint16_t* y, int M, int K, int N, int g, int ZW, int waves, int depth, int bpc, int sl, hipStream_t st,
-                         const AwqRowsFx* fxa) {
+int awq_launch_gemv_rows(const AwqGemvArgs& a, int waves, int depth, int bpc, int sl, const AwqRowsFx* fxa) {
+    const int M = a.M, K = a.K, N = a.N, g = a.g, ZW = a.width;
     if (!awq_gemv_rows_supports(M, K, N, g)) return AWQ_ERR_UNSUPPORTED;
     const int fx = fxa ? (fxa->norm_w ? FX_NORM : 0) | (fxa->res ? FX_RES : 0) | (fxa->pairs ? FX_PAIRS : 0) |
                              (fxa->pair_expert ? FX_GROUPED : 0) | (fxa->pair_scale ? FX_SCALE : 0) : 0;
@@ -796,11 +795,11 @@ int awq_launch_gemv_rows(const uint16_t* x, const int32_t* qweight, const uint16
     if ((int64_t)N * K / 2 >= ((int64_t)1 << 32) || (int64_t)N * ZW * 16 >= ((int64_t)1 << 32) || (int64_t)M * K * 2 >= ((int64_t)1 << 31))
         return AWQ_ERR_UNSUPPORTED;  // 32-bit byte offsets
     RowsParams p;
-    p.qweight = reinterpret_cast<const uint32_t*>(qweight);
-    p.qzeros = reinterpret_cast<const uint32_t*>(qzeros);
-    p.scales = reinterpret_cast<const half_t*>(scales);
-    p.x = reinterpret_cast<const half_t*>(x);
-    p.y = reinterpret_cast<half_t*>(y);
+    p.qweight = static_cast<const uint32_t*>(a.qweight);
+    p.qzeros = static_cast<const uint32_t*>(a.qzeros);
+    p.scales = reinterpret_cast<const half_t*>(a.scales);
+    p.x = reinterpret_cast<const half_t*>(a.x);
+    p.y = reinterpret_cast<half_t*>(a.y);
     p.M = M; p.K = K; p.N = N;
     p.KW = K / 8; p.ZW = ZW; p.SW = 8 * ZW;
     p.C = K / 32;
@@ -900,9 +899,9 @@ int awq_launch_gemv_rows(const uint16_t* x, const int32_t* qweight, const uint16
 #define AWQ_ROWS_CASE(SLV, DV, MV)                                                        \
     if (SL == SLV && depth == DV && M == MV) {                                            \
         if constexpr (MV == 1) {                                                          \
-            if (fx) return launch_rows_fx<SLV, DV>(fx, p, blocks, lds, st);               \
+            if (fx) return launch_rows_fx<SLV, DV>(fx, p, blocks, lds, a.stream);         \
         }                                                                                 \
-        return launch_rows<SLV, DV, MV>(p, blocks, lds, st);                              \
+        return launch_rows<SLV, DV, MV>(p, blocks, lds, a.stream);                        \
     }
     AWQ_ROWS_CASE(1, 1, 1) AWQ_ROWS_CASE(1, 1, 2) AWQ_ROWS_CASE(1, 1, 3) AWQ_ROWS_CASE(1, 1, 4)
     AWQ_ROWS_CASE(1, 2, 1) AWQ_ROWS_CASE(1, 2, 2) AWQ_ROWS_CASE(1, 2, 3) AWQ_ROWS_CASE(1, 2, 4)

@@ -32,6 +32,16 @@ def dequant_matmul_nk(x2d, wt):
     return torch.matmul(x2d, wt.t())
 
 
+def unless_unsupported(op, *args, **kwargs):
+    """op(*args, **kwargs), or None where the library has no kernel for the call (ERR_UNSUPPORTED): the caller takes its next route"""
+    try:
+        return op(*args, **kwargs)
+    except _lib.AwqHipError as e:
+        if e.code != _lib.ERR_UNSUPPORTED:
+            raise
+        return None
+
+
 # Below this many rows the call runs the decode / batched-decode kernels on the layout's own buffers (csrc/gemv_batch.hip takes any M in
 # launches of <= 128 rows, each streaming the matrix once: see prefill_min_rows; the reference switches to its batched kernel at 8
 # rows: gemv.py:168).  From it: PREFILL_IMPL.
@@ -126,24 +136,13 @@ class WQLinear_GEMV(nn.Module):
         if impl == "auto":
             impl = "repack" if prefill_route(rows, self.in_features, self.out_features) == "hand" else "two_pass"
         if not decode and impl == "repack" and self.out_features % 8 == 0:  # (the GEMM layout packs eight columns per word)
-            try:
-                out = ops.gemv_prefill_repack(inputs, self.qweight, self.scales, self.qzeros, self.group_size)
-            except _lib.AwqHipError as e:  # a shape the GEMM kernels refuse
-                if e.code != _lib.ERR_UNSUPPORTED:
-                    raise
-        if not decode and impl == "fused":
-            try:
-                out = ops.gemv_forward(inputs, self.qweight, self.scales, self.qzeros, self.group_size,
-                                       flags=ops.gemm_flags(kernel=ops.GEMV_KERNEL_PREFILL))
-            except _lib.AwqHipError as e:  # K % 64, group sizes below 64
-                if e.code != _lib.ERR_UNSUPPORTED:
-                    raise
-        if out is None and decode:
-            try:
-                out = ops.gemv_forward(inputs, self.qweight, self.scales, self.qzeros, self.group_size)
-            except _lib.AwqHipError as e:  # a shape no decode kernel of this layout takes (K % 128 with odd group sizes)
-                if e.code != _lib.ERR_UNSUPPORTED:
-                    raise
+            # (None: a shape the GEMM kernels refuse)
+            out = unless_unsupported(ops.gemv_prefill_repack, inputs, self.qweight, self.scales, self.qzeros, self.group_size)
+        if not decode and impl == "fused":  # (None: K % 64, group sizes below 64)
+            out = unless_unsupported(ops.gemv_forward, inputs, self.qweight, self.scales, self.qzeros, self.group_size,
+                                     flags=ops.gemm_flags(kernel=ops.GEMV_KERNEL_PREFILL))
+        if out is None and decode:  # (None: a shape no decode kernel of this layout takes -- K % 128 with odd group sizes)
+            out = unless_unsupported(ops.gemv_forward, inputs, self.qweight, self.scales, self.qzeros, self.group_size)
         if out is None:
             out = dequant_matmul_nk(inputs, ops.dequantize_weights_gemv(self.qweight, self.scales, self.qzeros, self.group_size))
         if input_dtype != torch.float16:

@@ -17,9 +17,9 @@ level with dequantise + dense fp16 GEMM (the reference's gemm.py:48-54 route, `"
 """
 import torch
 
-from ... import _lib, ops
+from ... import ops
 from ...utils.packing import calculate_zeros_width, pack_intweight_fast, quantize_int_weights_nk
-from .gemv import dequant_matmul_nk, prefill_min_rows, prefill_route
+from .gemv import dequant_matmul_nk, prefill_min_rows, prefill_route, unless_unsupported
 
 # below this many rows: the decode / batched-decode kernels (csrc/gemv_batch.hip in its GEMVFast form, launches of <= 128 rows, group
 # size 128; other group sizes: 16 rows, csrc/gemv_fast.hip); from it: PREFILL_IMPL
@@ -87,23 +87,17 @@ class WQLinear_GEMVFast(torch.nn.Module):
         out = None
         rows = inputs.shape[0]
         if (rows <= 16 or (rows < prefill_min_rows(self.in_features) and self.group_size == 128 and self.in_features % 128 == 0)) and self.out_features % 16 == 0:
-            try:
-                out = ops.gemv_fast_forward(inputs, self.qweight, self.scales, self.qzeros, self.group_size)
-            except _lib.AwqHipError as e:  # a shape the decode kernel does not take (K % 128, unusual group sizes)
-                if e.code != _lib.ERR_UNSUPPORTED:
-                    raise
+            # (None: a shape the decode kernel does not take -- K % 128, unusual group sizes)
+            out = unless_unsupported(ops.gemv_fast_forward, inputs, self.qweight, self.scales, self.qzeros, self.group_size)
         impl = self.PREFILL_IMPL
         if impl == "auto":
             impl = "fused" if prefill_route(rows, self.in_features, self.out_features) == "hand" else "two_pass"
         if out is None and impl == "fused":
             # prefill-sized batches: two hand-written launches on THIS layout's buffers (round 6) -- the words transposed into a
             # temporary of the call, then the fused MFMA GEMM with the layout's w * s + qzeros arithmetic (the same effective weights
-            # the decode kernel uses).  Nothing resident, no vendor GEMM.
-            try:
-                out = ops.gemv_fast_prefill(inputs, self.qweight, self.scales, self.qzeros, self.group_size)
-            except _lib.AwqHipError as e:  # K % 64, group sizes below 64, N % 8: the two-pass route below
-                if e.code != _lib.ERR_UNSUPPORTED:
-                    raise
+            # the decode kernel uses).  Nothing resident, no vendor GEMM.  (None: K % 64, group sizes below 64, N % 8 -- the two-pass
+            # route below)
+            out = unless_unsupported(ops.gemv_fast_prefill, inputs, self.qweight, self.scales, self.qzeros, self.group_size)
         if out is None:
             # the reference's own two-pass route (awq/modules/linear/gemm.py:48-54): dequantise (hand-written kernel) into a temporary +
             # a dense fp16 GEMM; explicit (`PREFILL_IMPL = "two_pass"`) or for the shapes the fused kernel refuses

@@ -283,47 +283,55 @@ def grouped_gemm_prefill_ex(x, qweight, scales, qzeros, seg_offsets, row_map, x_
     return y
 
 
-def gemv_forward(x2d, qweight, scales, qzeros, group_size, flags=0):
-    """GEMV layout (qweight [N, K/8], qzeros [N, ZW], scales [N, 8*ZW]): y [M, N] fp16 = x2d @ W^T
-    (awq_gemv_forward).  M is processed in chunks that fit the kernel (<= 16 rows and the LDS)."""
+def _gemv_operands(name, x2d, qweight, scales, qzeros, halve=False):
+    """GEMV layout: the operands of the wrapper `name`, checked (on a HIP device, fp16 activations, matching shapes) and contiguous,
+    a fresh output [M, N] (halve: [M, N / 2]) and the sizes the library takes: (x2d, qweight, scales, qzeros, y, M, K, N, ZW)"""
     _require_gpu(x2d, qweight, scales, qzeros)
     if x2d.dtype != torch.float16:
-        raise _lib.AwqHipError("gemv_forward expects fp16 activations")
+        raise _lib.AwqHipError(f"{name} expects fp16 activations")
     x2d, qweight, scales, qzeros = x2d.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
     M, K = x2d.shape
     N, ZW = qweight.shape[0], qzeros.shape[1]
     if qweight.shape[1] * 8 != K or scales.shape != (N, ZW * 8):
-        raise _lib.AwqHipError(f"gemv_forward: shape mismatch x{tuple(x2d.shape)} qweight{tuple(qweight.shape)} "
+        raise _lib.AwqHipError(f"{name}: shape mismatch x{tuple(x2d.shape)} qweight{tuple(qweight.shape)} "
                                f"qzeros{tuple(qzeros.shape)} scales{tuple(scales.shape)}")
-    y = torch.empty((M, N), dtype=torch.float16, device=x2d.device)
-    if M == 0:
-        return y
-    L = _lib.lib()
-    if (flags & 0xF) == GEMV_KERNEL_PREFILL:
-        # explicit only: ONE call of the register-decoded MFMA GEMM on this layout's own buffers (any M); AUTO keeps the
-        # 16-row chunks of the decode kernels (include/awq_hip.h: the kernel is latency-bound below ~2000 rows)
-        with torch.cuda.device(x2d.device):
-            rc = L.awq_gemv_forward(_ptr(x2d), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(y), M, K, N, group_size, ZW, flags,
-                                    _stream())
-        _lib.check(rc, "awq_gemv_forward")
-        return y
-    kern = flags & 0xF
-    if kern == GEMV_KERNEL_BATCH or (kern == 0 and L.awq_gemv_auto_kernel(M, K, N, group_size) == GEMV_KERNEL_BATCH):
-        # round 5: the batched kernel (csrc/gemv_batch.hip) takes ANY M in one call (launches of <= 128 rows inside the library)
-        with torch.cuda.device(x2d.device):
-            rc = L.awq_gemv_forward(_ptr(x2d), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(y), M, K, N, group_size, ZW, flags,
-                                    _stream())
-        _lib.check(rc, "awq_gemv_forward")
-        return y
-    chunk = 16
-    while chunk > 1 and L.awq_gemv_lds_bytes(chunk, K, ZW) > 160 * 1024:
-        chunk //= 2
+    y = torch.empty((M, N // 2 if halve else N), dtype=torch.float16, device=x2d.device)
+    return x2d, qweight, scales, qzeros, y, M, K, N, ZW
+
+
+def _forward_rows(fn, x2d, qweight, scales, qzeros, y, chunk, *sizes_flags):
+    """awq_gemv_forward / awq_gemv_fast_forward (`fn`) on `chunk` rows of x2d at a time; the first code that is not 0, else 0"""
+    M = x2d.shape[0]
     with torch.cuda.device(x2d.device):
         for m0 in range(0, M, chunk):
             m1 = min(M, m0 + chunk)
-            rc = L.awq_gemv_forward(_ptr(x2d[m0:m1]), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(y[m0:m1]),
-                                    m1 - m0, K, N, group_size, ZW, flags, _stream())
-            _lib.check(rc, "awq_gemv_forward")
+            rc = fn(_ptr(x2d[m0:m1]), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(y[m0:m1]), m1 - m0, *sizes_flags, _stream())
+            if rc:
+                return rc
+    return 0
+
+
+def _decode_chunk(lds_bytes):
+    """Rows per call of the 16-row decode kernels: at most 16, halved while the kernel's LDS (lds_bytes(rows)) exceeds 160 KiB"""
+    chunk = 16
+    while chunk > 1 and lds_bytes(chunk) > 160 * 1024:
+        chunk //= 2
+    return chunk
+
+
+def gemv_forward(x2d, qweight, scales, qzeros, group_size, flags=0):
+    """GEMV layout (qweight [N, K/8], qzeros [N, ZW], scales [N, 8*ZW]): y [M, N] fp16 = x2d @ W^T
+    (awq_gemv_forward).  M is processed in chunks that fit the kernel (<= 16 rows and the LDS)."""
+    x2d, qweight, scales, qzeros, y, M, K, N, ZW = _gemv_operands("gemv_forward", x2d, qweight, scales, qzeros)
+    if M == 0:
+        return y
+    L = _lib.lib()
+    kern = flags & 0xF
+    # ONE call: PREFILL (explicit only: the register-decoded MFMA GEMM, any M; latency-bound below ~2000 rows, include/awq_hip.h) and
+    # the batched kernel (csrc/gemv_batch.hip: launches of <= 128 rows inside the library), named or the library's AUTO choice
+    one_call = kern in (GEMV_KERNEL_PREFILL, GEMV_KERNEL_BATCH) or (kern == 0 and gemv_auto_kernel(M, K, N, group_size) == GEMV_KERNEL_BATCH)
+    chunk = M if one_call else _decode_chunk(lambda rows: L.awq_gemv_lds_bytes(rows, K, ZW))
+    _lib.check(_forward_rows(L.awq_gemv_forward, x2d, qweight, scales, qzeros, y, chunk, K, N, group_size, ZW, flags), "awq_gemv_forward")
     return y
 
 
@@ -344,17 +352,8 @@ def gemv_forward_ex(x2d, qweight, scales, qzeros, group_size, norm_weight=None, 
     fp16(fp16(W x) + add_residual); silu_pairs: rows (2 i, 2 i + 1) are (gate_i, up_i), returns [1, N / 2] =
     silu(gate) * up.  Raises AwqHipError with code AWQ_ERR_UNSUPPORTED (-3) for shapes the row-streaming kernel
     does not take (M > 1, K > 16384): the caller then runs the separate launches."""
-    _require_gpu(x2d, qweight, scales, qzeros, norm_weight, add_residual)
-    if x2d.dtype != torch.float16:
-        raise _lib.AwqHipError("gemv_forward_ex expects fp16 activations")
-    x2d, qweight, scales, qzeros = x2d.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
-    M, K = x2d.shape
-    N, ZW = qweight.shape[0], qzeros.shape[1]
-    if qweight.shape[1] * 8 != K or scales.shape != (N, ZW * 8):
-        raise _lib.AwqHipError(f"gemv_forward_ex: shape mismatch x{tuple(x2d.shape)} qweight{tuple(qweight.shape)} "
-                               f"qzeros{tuple(qzeros.shape)} scales{tuple(scales.shape)}")
-    n_out = N // 2 if silu_pairs else N
-    y = torch.empty((M, n_out), dtype=torch.float16, device=x2d.device)
+    _require_gpu(norm_weight, add_residual)
+    x2d, qweight, scales, qzeros, y, M, K, N, ZW = _gemv_operands("gemv_forward_ex", x2d, qweight, scales, qzeros, halve=silu_pairs)
     if add_residual is not None and (add_residual.shape != y.shape or add_residual.dtype != torch.float16
                                      or not add_residual.is_contiguous()):
         raise _lib.AwqHipError("gemv_forward_ex: add_residual must be a contiguous fp16 [M, N] tensor")
@@ -375,17 +374,20 @@ def gemv_forward_ex(x2d, qweight, scales, qzeros, group_size, norm_weight=None, 
     return y
 
 
-def dequantize_weights_gemv(qweight, scales, qzeros, group_size):
-    """GEMV-layout buffers -> fp16 W^T [N, K] (awq_dequantize_weights_gemv)."""
+def _dequantize_nk(name, qweight, scales, qzeros, N, K, *sizes):
+    """fp16 W^T [N, K] of GEMV- or GEMVFast-layout buffers by the library's dequantiser `name`"""
     _require_gpu(qweight, scales, qzeros)
     qweight, scales, qzeros = qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
-    N, K = qweight.shape[0], qweight.shape[1] * 8
     out = torch.empty((N, K), dtype=torch.float16, device=qweight.device)
     with torch.cuda.device(qweight.device):
-        _lib.check(_lib.lib().awq_dequantize_weights_gemv(_ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(out), K, N,
-                                                          group_size, qzeros.shape[1], _stream()),
-                   "awq_dequantize_weights_gemv")
+        _lib.check(getattr(_lib.lib(), name)(_ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(out), K, N, *sizes, _stream()), name)
     return out
+
+
+def dequantize_weights_gemv(qweight, scales, qzeros, group_size):
+    """GEMV-layout buffers -> fp16 W^T [N, K] (awq_dequantize_weights_gemv)."""
+    return _dequantize_nk("awq_dequantize_weights_gemv", qweight, scales, qzeros, qweight.shape[0], qweight.shape[1] * 8, group_size,
+                          qzeros.shape[1])
 
 
 def repack_gemv_to_gemm(qweight, scales, qzeros, group_size):
@@ -568,41 +570,42 @@ def fused_topk(gating_output, topk, renormalize):
     return w, ids.to(torch.int32)
 
 
-def gemv_fast_forward(x2d, qweight, scales, qzeros, group_size, flags=0):
-    """GEMVFast layout (qweight int16 [N/4, K], scales / qzeros fp16 [8*ZW, N]): y [M, N] fp16
-    (awq_gemv_fast_forward).  AUTO: the batched kernel (csrc/gemv_batch.hip, GEMVFast form) from five rows -- at every batch size while
-    2048 < K <= 4096 -- in one call; otherwise the 16-row kernel (csrc/gemv_fast.hip) in chunks of <= 16 rows."""
+def _gemv_fast_operands(name, x2d, qweight, scales, qzeros):
+    """GEMVFast layout: as _gemv_operands; (x2d, qweight, scales, qzeros, y, M, K, N, GP), GP = the rows of scales / qzeros"""
     _require_gpu(x2d, qweight, scales, qzeros)
     if x2d.dtype != torch.float16:
-        raise _lib.AwqHipError("gemv_fast_forward expects fp16 activations")
+        raise _lib.AwqHipError(f"{name} expects fp16 activations")
     x2d, qweight, scales, qzeros = x2d.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
     M, K = x2d.shape
     N, GP = qweight.shape[0] * 4, scales.shape[0]
     if qweight.shape[1] != K or scales.shape != (GP, N) or qzeros.shape != (GP, N):
-        raise _lib.AwqHipError(f"gemv_fast_forward: shape mismatch x{tuple(x2d.shape)} qweight{tuple(qweight.shape)} "
+        raise _lib.AwqHipError(f"{name}: shape mismatch x{tuple(x2d.shape)} qweight{tuple(qweight.shape)} "
                                f"scales{tuple(scales.shape)}")
     y = torch.empty((M, N), dtype=torch.float16, device=x2d.device)
+    return x2d, qweight, scales, qzeros, y, M, K, N, GP
+
+
+def gemv_fast_forward(x2d, qweight, scales, qzeros, group_size, flags=0):
+    """GEMVFast layout (qweight int16 [N/4, K], scales / qzeros fp16 [8*ZW, N]): y [M, N] fp16
+    (awq_gemv_fast_forward).  AUTO: the batched kernel (csrc/gemv_batch.hip, GEMVFast form) from five rows -- at every batch size while
+    2048 < K <= 4096 -- in one call; otherwise the 16-row kernel (csrc/gemv_fast.hip) in chunks of <= 16 rows."""
+    x2d, qweight, scales, qzeros, y, M, K, N, GP = _gemv_fast_operands("gemv_fast_forward", x2d, qweight, scales, qzeros)
     if M == 0:
         return y
     L = _lib.lib()
+
+    def run(chunk):
+        return _forward_rows(L.awq_gemv_fast_forward, x2d, qweight, scales, qzeros, y, chunk, K, N, group_size, GP, flags)
+
     kern = flags & 0xF
-    if (kern == GEMV_KERNEL_BATCH or (kern == 0 and M >= 5)):
-        # round 5: the batched kernel in its GEMVFast form takes ANY M in one call (launches of <= 128 rows inside the library); shapes it
-        # refuses (group sizes other than 128) fall through to the 16-row kernel in chunks
-        with torch.cuda.device(x2d.device):
-            rc = L.awq_gemv_fast_forward(_ptr(x2d), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(y), M, K, N, group_size, GP, flags, _stream())
+    if kern == GEMV_KERNEL_BATCH or (kern == 0 and M >= 5):
+        # the batched kernel in its GEMVFast form takes ANY M in one call (launches of <= 128 rows inside the library); shapes it
+        # refuses (group sizes other than 128) fall through to the 16-row kernel in chunks, unless the caller named it
+        rc = run(M)
         if rc != _lib.ERR_UNSUPPORTED or kern == GEMV_KERNEL_BATCH:
             _lib.check(rc, "awq_gemv_fast_forward")
             return y
-    chunk = 16
-    while chunk > 1 and L.awq_gemv_fast_lds_bytes_c(chunk, K, group_size) > 160 * 1024:
-        chunk //= 2
-    with torch.cuda.device(x2d.device):
-        for m0 in range(0, M, chunk):
-            m1 = min(M, m0 + chunk)
-            rc = L.awq_gemv_fast_forward(_ptr(x2d[m0:m1]), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(y[m0:m1]),
-                                         m1 - m0, K, N, group_size, GP, flags, _stream())
-            _lib.check(rc, "awq_gemv_fast_forward")
+    _lib.check(run(_decode_chunk(lambda rows: L.awq_gemv_fast_lds_bytes_c(rows, K, group_size))), "awq_gemv_fast_forward")
     return y
 
 
@@ -611,15 +614,7 @@ def gemv_fast_prefill(x2d, qweight, scales, qzeros, group_size, flags=0):
     (awq_gemv_fast_prefill: the packed words transposed into a temporary of the call, then the register-decoded MFMA GEMM with this
     format's scales / fp16 zero terms) -- the role of awq_v2_ext.gemm_forward_cuda_prefill (awq/modules/linear/gemv_fast.py:203-206).
     Raises AwqHipError with code ERR_UNSUPPORTED for shapes the fused kernel does not take (K % 64, group_size % 64, N % 8)."""
-    _require_gpu(x2d, qweight, scales, qzeros)
-    if x2d.dtype != torch.float16:
-        raise _lib.AwqHipError("gemv_fast_prefill expects fp16 activations")
-    x2d, qweight, scales, qzeros = x2d.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
-    M, K = x2d.shape
-    N, GP = qweight.shape[0] * 4, scales.shape[0]
-    if qweight.shape[1] != K or scales.shape != (GP, N) or qzeros.shape != (GP, N):
-        raise _lib.AwqHipError(f"gemv_fast_prefill: shape mismatch x{tuple(x2d.shape)} qweight{tuple(qweight.shape)} scales{tuple(scales.shape)}")
-    y = torch.empty((M, N), dtype=torch.float16, device=x2d.device)
+    x2d, qweight, scales, qzeros, y, M, K, N, GP = _gemv_fast_operands("gemv_fast_prefill", x2d, qweight, scales, qzeros)
     if M == 0:
         return y
     tmp = torch.empty((K, max(N // 8, 1)), dtype=torch.int32, device=x2d.device)  # GEMM-layout words of the same integers: a temporary of the call
@@ -643,14 +638,7 @@ def repack_gemvfast_to_gemm(qweight):
 
 def dequantize_weights_gemv_fast(qweight, scales, qzeros, group_size):
     """GEMVFast-layout buffers -> fp16 W^T [N, K] (awq_dequantize_weights_gemv_fast)."""
-    _require_gpu(qweight, scales, qzeros)
-    qweight, scales, qzeros = qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
-    N, K = qweight.shape[0] * 4, qweight.shape[1]
-    out = torch.empty((N, K), dtype=torch.float16, device=qweight.device)
-    with torch.cuda.device(qweight.device):
-        _lib.check(_lib.lib().awq_dequantize_weights_gemv_fast(_ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(out), K, N,
-                                                               group_size, _stream()), "awq_dequantize_weights_gemv_fast")
-    return out
+    return _dequantize_nk("awq_dequantize_weights_gemv_fast", qweight, scales, qzeros, qweight.shape[0] * 4, qweight.shape[1], group_size)
 
 
 def auto_kernel(M, K, N, group_size):
