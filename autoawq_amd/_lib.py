@@ -152,6 +152,9 @@ SIGNATURES = {
     "awq_verify_attention_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "awq_verify_attention_splits": (c_int, [c_int64] * 5),
     "awq_verify_attention_rows": (c_int, [c_void_p] * 5 + [c_int64] * 7 + [c_float, c_void_p, c_size_t, c_void_p]),
+    "awq_rope_kv_append_rows_n": (c_int, [c_void_p] * 8 + [c_int64] * 7 + [c_void_p]),
+    "awq_rope_kv_append_rows_n_fp8": (c_int, [c_void_p] * 10 + [c_int64] * 7 + [c_void_p]),
+    "awq_prefill_attention_rows": (c_int, [c_void_p] * 6 + [c_int64] * 7 + [c_float, c_float, c_void_p, c_void_p]),
     "awq_spec_accept": (c_int, [ctypes.POINTER(AwqSpecArgs)]),
     "awq_ngram_draft": (c_int, [ctypes.POINTER(AwqSpecArgs)]),
 }

@@ -172,6 +172,7 @@ struct AwqAppendArgs {
     const float *cos_t, *sin_t;
     const int32_t* pos_dev = nullptr;  // device position word: one for the batch, or [B] with `rows`; null: start_pos
     bool rows = false;
+    const int32_t* count_dev = nullptr;  // with `rows`: [B] new tokens per sequence -- slots s >= count_dev[b] write nothing
     int64_t start_pos = 0, B, S, Hq, Hkv, D, rot, Tmax;
     hipStream_t stream;
 };

@@ -762,6 +762,31 @@ int awq_rope_kv_append_rows_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k
     return rope_kv_append(a, true);
 }
 
+int awq_rope_kv_append_rows_n(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, const float* cos_table,
+                              const float* sin_table, const int32_t* pos_rows, const int32_t* count_rows, int64_t B, int64_t S,
+                              int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim, int64_t max_seq, void* stream) {
+    AwqAppendArgs a;
+    a.qkv = qkv, a.q_out = q_out, a.k_cache = k_cache, a.v_cache = v_cache, a.cos_t = cos_table, a.sin_t = sin_table;
+    a.pos_dev = pos_rows, a.rows = true, a.count_dev = count_rows;
+    a.B = B, a.S = S, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.rot = rotary_dim, a.Tmax = max_seq;
+    a.stream = static_cast<hipStream_t>(stream);
+    if (B > 0 && S > 0 && !count_rows) return AWQ_ERR_NULL;
+    return rope_kv_append(a, false);
+}
+
+int awq_rope_kv_append_rows_n_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k_cache, uint8_t* v_cache, float* k_scale,
+                                  float* v_scale, const float* cos_table, const float* sin_table, const int32_t* pos_rows,
+                                  const int32_t* count_rows, int64_t B, int64_t S, int64_t n_heads, int64_t n_kv_heads,
+                                  int64_t head_dim, int64_t rotary_dim, int64_t max_seq, void* stream) {
+    AwqAppendArgs a;
+    a.qkv = qkv, a.q_out = q_out, a.k_cache = k_cache, a.v_cache = v_cache, a.k_scale = k_scale, a.v_scale = v_scale;
+    a.cos_t = cos_table, a.sin_t = sin_table, a.pos_dev = pos_rows, a.rows = true, a.count_dev = count_rows;
+    a.B = B, a.S = S, a.Hq = n_heads, a.Hkv = n_kv_heads, a.D = head_dim, a.rot = rotary_dim, a.Tmax = max_seq;
+    a.stream = static_cast<hipStream_t>(stream);
+    if (B > 0 && S > 0 && !count_rows) return AWQ_ERR_NULL;
+    return rope_kv_append(a, true);
+}
+
 size_t awq_decode_attention_workspace_bytes(int64_t B, int64_t n_heads) {
     if (B <= 0 || n_heads <= 0) return 0;
     return awq_decode_attention_workspace_bytes_impl((int)B, (int)n_heads, 64);

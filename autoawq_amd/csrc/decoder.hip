@@ -181,15 +181,20 @@ __global__ __launch_bounds__(256) void awq_rmsnorm_kernel(const half_t* __restri
 // writes q to q_out [B*S, Hq, D], k / v to the caches [B, Tmax, Hkv, D] at row start + s.
 // ROWS (awq_rope_kv_append_rows): every sequence b has its own start, pos_dev[b] ([B] int32 on the device, never NULL) --
 // batches of prompts of different lengths (modules/fused/decode.py); clamped to [0, Tmax - 1] like the shared one.
+// COUNTS (awq_rope_kv_append_rows_n*): ROWS with count_dev[b] new tokens in sequence b -- the blocks of slots s >= count_dev[b] leave
+// without writing anything (the clamp above would otherwise put a pad slot of a sequence that ends at Tmax on its last real row).
 // KV8 (awq_rope_kv_append*_fp8, D = 128: one wave): a k / v block computes its fp16 row exactly as above into LDS, then lanes
 // (r, c) quantize it 16 lanes x 8 values (kv8_quant_row) and row 0 writes the 128 codes and the scale.
-template <bool ROWS, bool KV8, class CacheT>
+template <bool ROWS, bool KV8, bool COUNTS = false, class CacheT>
 AWQ_DEV void rope_kv_append_body(const half_t* qkv, half_t* q_out, CacheT* k_cache,
                                  CacheT* v_cache, const float* cos_t, const float* sin_t,
                                  const int* pos_dev, int start_pos, int S, int Hq, int Hkv, int D, int rot, int Tmax,
-                                 float* k_scale, float* v_scale) {
+                                 float* k_scale, float* v_scale, const int* count_dev = nullptr) {
     const int slot = blockIdx.x % (Hq + 2 * Hkv), tok = blockIdx.x / (Hq + 2 * Hkv);
     const int b = tok / S, s = tok % S;
+    if constexpr (COUNTS) {
+        if (s >= count_dev[b]) return;  // (block-uniform)
+    }
     // A device-side position (hipGraph replay) is not seen by the host checks: clamp it to the cache so that a
     // replay past max_seq_len overwrites the last row instead of memory behind the cache / the cos-sin tables
     // (the caller is expected to roll the window before that: modules/fused/model.py).
@@ -248,6 +253,25 @@ __global__ __launch_bounds__(64) void awq_rope_kv_append_fp8_kernel(const half_t
                                                                    int Hkv, int rot, int Tmax) {
     rope_kv_append_body<ROWS, true>(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos_dev, start_pos, S, Hq, Hkv, 128, rot, Tmax,
                                     k_scale, v_scale);
+}
+
+__global__ __launch_bounds__(128) void awq_rope_kv_append_n_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ q_out,
+                                                                  half_t* __restrict__ k_cache, half_t* __restrict__ v_cache,
+                                                                  const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                                  const int* __restrict__ pos_dev, const int* __restrict__ count_dev,
+                                                                  int S, int Hq, int Hkv, int D, int rot, int Tmax) {
+    rope_kv_append_body<true, false, true>(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos_dev, 0, S, Hq, Hkv, D, rot, Tmax, nullptr,
+                                           nullptr, count_dev);
+}
+
+__global__ __launch_bounds__(64) void awq_rope_kv_append_n_fp8_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ q_out,
+                                                                     uint8_t* __restrict__ k_cache, uint8_t* __restrict__ v_cache,
+                                                                     float* __restrict__ k_scale, float* __restrict__ v_scale,
+                                                                     const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                                     const int* __restrict__ pos_dev, const int* __restrict__ count_dev,
+                                                                     int S, int Hq, int Hkv, int rot, int Tmax) {
+    rope_kv_append_body<true, true, true>(qkv, q_out, k_cache, v_cache, cos_t, sin_t, pos_dev, 0, S, Hq, Hkv, 128, rot, Tmax, k_scale,
+                                          v_scale, count_dev);
 }
 
 // ---------------------------------------------------------------- single-query attention over the cache
@@ -621,6 +645,7 @@ int awq_launch_rope_kv_append(const AwqAppendArgs& a) {
     if (B < 0 || S < 0 || Hq < 1 || Hkv < 1 || D < 2 || D % 2 || D > 256 || rot < 0 || rot > D || rot % 2)
         return AWQ_ERR_BAD_SHAPE;
     if (a.rows && !a.pos_dev) return AWQ_ERR_NULL;
+    if (a.count_dev && !a.rows) return AWQ_ERR_BAD_SHAPE;
     if (!a.pos_dev && (start_pos < 0 || start_pos + S > Tmax)) return AWQ_ERR_BAD_SHAPE;
     const bool kv8 = a.k_scale != nullptr;
     if (kv8 && !a.v_scale) return AWQ_ERR_NULL;
@@ -629,7 +654,15 @@ int awq_launch_rope_kv_append(const AwqAppendArgs& a) {
     const unsigned blocks = (unsigned)((int64_t)B * S * (Hq + 2 * Hkv));
     const half_t* qkv = reinterpret_cast<const half_t*>(a.qkv);
     half_t* q_out = reinterpret_cast<half_t*>(a.q_out);
-    if (kv8)
+    if (a.count_dev && kv8)
+        hipLaunchKernelGGL(awq_rope_kv_append_n_fp8_kernel, dim3(blocks), dim3(64), 0, a.stream, qkv, q_out,
+                           static_cast<uint8_t*>(a.k_cache), static_cast<uint8_t*>(a.v_cache), a.k_scale, a.v_scale, a.cos_t, a.sin_t,
+                           a.pos_dev, a.count_dev, S, Hq, Hkv, rot, Tmax);
+    else if (a.count_dev)
+        hipLaunchKernelGGL(awq_rope_kv_append_n_kernel, dim3(blocks), dim3(D / 2), 0, a.stream, qkv, q_out,
+                           static_cast<half_t*>(a.k_cache), static_cast<half_t*>(a.v_cache), a.cos_t, a.sin_t, a.pos_dev, a.count_dev, S,
+                           Hq, Hkv, D, rot, Tmax);
+    else if (kv8)
         hipLaunchKernelGGL(a.rows ? awq_rope_kv_append_fp8_kernel<true> : awq_rope_kv_append_fp8_kernel<false>, dim3(blocks), dim3(64),
                            0, a.stream, qkv, q_out, static_cast<uint8_t*>(a.k_cache), static_cast<uint8_t*>(a.v_cache), a.k_scale,
                            a.v_scale, a.cos_t, a.sin_t, a.pos_dev, start_pos, S, Hq, Hkv, rot, Tmax);

@@ -48,6 +48,9 @@ struct PrefillAttnParams {
     half_t* out;
     const float* alibi;  // [Hq] or null
     int B, S, Hq, Hkv, Tmax, start;
+    const int* pos_rows;    // ROWS: [B] start of every batch entry (instead of `start`)
+    const int* count_rows;  // ROWS: [B] new rows of every batch entry (instead of S), 0 .. S
+    int max_end;            // ROWS: the host's bound of pos_rows[b] + count_rows[b], <= Tmax
     int qblocks, per_group, groups;  // blocks of 128 rows; blocks per (batch, kv head); number of (batch, kv head) pairs
     float scale_log2;    // scale * log2(e)   (no soft cap)
     float scale, softcap;  // soft cap: cap * tanh(s * scale / cap)
@@ -60,7 +63,10 @@ AWQ_DEV uint32_t pack_h2(float a, float b) {
     return h22u(h);
 }
 
-template <bool MODS>  // MODS: ALiBi slopes and / or a soft cap on the scores
+// ROWS (awq_prefill_attention_rows): batch entry b starts at pos_rows[b] and has count_rows[b] <= S new rows; the slots behind
+// them are neither loaded nor stored, and a block whose first row is one of them leaves at once.  Same tile walk (from row 0,
+// tiles of 64), so equal rows give the bits of the shared form.  Both words are clamped to the host's bound max_end.
+template <bool MODS, bool ROWS = false>  // MODS: ALiBi slopes and / or a soft cap on the scores
 __global__ __launch_bounds__(256, 2) void awq_prefill_attn_kernel(PrefillAttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -78,20 +84,26 @@ __global__ __launch_bounds__(256, 2) void awq_prefill_attn_kernel(PrefillAttnPar
     const int qb = p.qblocks - 1 - within / hq_per;
     const int h = kvh * hq_per + within % hq_per;
     const int q0 = qb * BQ;
+    int start = p.start, count = p.S;
+    if constexpr (ROWS) {
+        start = max(0, min(p.pos_rows[b], p.max_end));
+        count = max(0, min(p.count_rows[b], min(p.S, p.max_end - start)));
+        if (q0 >= count) return;  // (block-uniform) nothing but pad slots: before any load
+    }
 
     const uint32_t q_row_bytes = (uint32_t)p.Hq * HD * 2u, kv_row_bytes = (uint32_t)p.Hkv * HD * 2u;
-    const int kv_len = p.start + p.S;
+    const int kv_len = start + count;
     const rsrc_t qres = mk_rsrc(p.q + (size_t)b * p.S * p.Hq * HD, (uint32_t)p.S * q_row_bytes);
     const rsrc_t kres = mk_rsrc(p.k + (size_t)b * p.Tmax * p.Hkv * HD, (uint32_t)kv_len * kv_row_bytes);  // rows >= kv_len read 0
     const rsrc_t vres = mk_rsrc(p.v + (size_t)b * p.Tmax * p.Hkv * HD, (uint32_t)kv_len * kv_row_bytes);
 
-    // ---- Q fragments: query 16 qt + j of this wave, 16 B at d = 32 ks + 8 kb (rows >= S: zeros, never stored)
+    // ---- Q fragments: query 16 qt + j of this wave, 16 B at d = 32 ks + 8 kb (rows >= S, ROWS: >= count: zeros, never stored)
     const int qw0 = q0 + 32 * wave;
     u32x4v qf[2][4];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
         const uint32_t row = (uint32_t)(qw0 + 16 * qt + j);
-        const uint32_t off = row < (uint32_t)p.S ? row * q_row_bytes + (uint32_t)h * (HD * 2u) + 16u * (uint32_t)kb : OOB;
+        const uint32_t off = row < (uint32_t)count ? row * q_row_bytes + (uint32_t)h * (HD * 2u) + 16u * (uint32_t)kb : OOB;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
             qf[qt][ks] = __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(qres, off, 64 * ks, 0));
@@ -168,13 +180,13 @@ __global__ __launch_bounds__(256, 2) void awq_prefill_attn_kernel(PrefillAttnPar
     }
     int qpos[2];
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt) qpos[qt] = p.start + qw0 + 16 * qt + j;
-    const int qpos_wave_min = p.start + qw0;
+    for (int qt = 0; qt < 2; ++qt) qpos[qt] = start + qw0 + 16 * qt + j;
+    const int qpos_wave_min = start + qw0;
     float slope = 0.f;
     if constexpr (MODS) slope = p.alibi ? p.alibi[h] * 1.44269504088896f : 0.f;
 
-    const int last_row = min(q0 + BQ, p.S) - 1;
-    const int ntiles = (p.start + last_row) / BKV + 1;
+    const int last_row = min(q0 + BQ, count) - 1;
+    const int ntiles = (start + last_row) / BKV + 1;
 
     load_k(0);
     load_v(0);
@@ -316,7 +328,7 @@ __global__ __launch_bounds__(256, 2) void awq_prefill_attn_kernel(PrefillAttnPar
         const float l = lacc[qt][0];  // every row of the ones product is the query's sum, over all four lanes' slots
         const float inv = 1.0f / l;
         const int row = qw0 + 16 * qt + j;
-        if (row >= p.S) continue;
+        if (row >= count) continue;
         half_t* dst = p.out + ((size_t)(b * p.S + row) * p.Hq + h) * HD + 4 * kb;
 #pragma unroll
         for (int dt = 0; dt < 8; ++dt) {
@@ -330,6 +342,29 @@ __global__ __launch_bounds__(256, 2) void awq_prefill_attn_kernel(PrefillAttnPar
 }
 
 }  // namespace
+
+// what both entry points launch: p.start / p.S (shared) or p.pos_rows / p.count_rows / p.max_end (rows) already set
+template <bool ROWS>
+static int launch_prefill_attn(PrefillAttnParams& p, float scale, float softcap, void* stream) {
+    p.qblocks = (p.S + BQ - 1) / BQ;
+    p.per_group = p.qblocks * (p.Hq / p.Hkv);
+    p.groups = p.B * p.Hkv;
+    p.scale = scale;
+    p.softcap = softcap;
+    p.scale_log2 = scale * 1.44269504088896f;
+    const int rounds = (p.groups + 7) / 8;
+    const dim3 grid((unsigned)(8 * rounds * p.per_group));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    static std::atomic<unsigned long long> opted0{0}, opted1{0};
+    if (p.alibi || softcap > 0.f) {
+        (void)awq_lds_opt_in(reinterpret_cast<const void*>(&awq_prefill_attn_kernel<true, ROWS>), opted1, LDS_BYTES);
+        hipLaunchKernelGGL((awq_prefill_attn_kernel<true, ROWS>), grid, dim3(256), LDS_BYTES, st, p);
+    } else {
+        (void)awq_lds_opt_in(reinterpret_cast<const void*>(&awq_prefill_attn_kernel<false, ROWS>), opted0, LDS_BYTES);
+        hipLaunchKernelGGL((awq_prefill_attn_kernel<false, ROWS>), grid, dim3(256), LDS_BYTES, st, p);
+    }
+    return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
+}
 
 // q / out [B, S, Hq, 128] fp16, k / v caches [>= B, Tmax, Hkv, 128] fp16 holding rows 0 .. start + S - 1 of every batch entry;
 // scale: the score factor (1 / sqrt(128) by default); softcap 0 = none; alibi_slopes [Hq] fp32 on the device or null.
@@ -354,22 +389,39 @@ int awq_prefill_attention(const uint16_t* q, const uint16_t* k_cache, const uint
     p.out = reinterpret_cast<half_t*>(out);
     p.alibi = alibi_slopes;
     p.B = B; p.S = S; p.Hq = Hq; p.Hkv = Hkv; p.Tmax = Tmax; p.start = start;
-    p.qblocks = (S + BQ - 1) / BQ;
-    p.per_group = p.qblocks * (Hq / Hkv);
-    p.groups = B * Hkv;
-    p.scale = scale;
-    p.softcap = softcap;
-    p.scale_log2 = scale * 1.44269504088896f;
-    const int rounds = (p.groups + 7) / 8;
-    const dim3 grid((unsigned)(8 * rounds * p.per_group));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    static std::atomic<unsigned long long> opted0{0}, opted1{0};
-    if (alibi_slopes || softcap > 0.f) {
-        (void)awq_lds_opt_in(reinterpret_cast<const void*>(&awq_prefill_attn_kernel<true>), opted1, LDS_BYTES);
-        hipLaunchKernelGGL((awq_prefill_attn_kernel<true>), grid, dim3(256), LDS_BYTES, st, p);
-    } else {
-        (void)awq_lds_opt_in(reinterpret_cast<const void*>(&awq_prefill_attn_kernel<false>), opted0, LDS_BYTES);
-        hipLaunchKernelGGL((awq_prefill_attn_kernel<false>), grid, dim3(256), LDS_BYTES, st, p);
-    }
-    return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
+    p.pos_rows = p.count_rows = nullptr;
+    p.max_end = start + S;
+    return launch_prefill_attn<false>(p, scale, softcap, stream);
+}
+
+// The shared form with one start and one count per batch entry, read on the device: pos_rows / count_rows [B] int32.  Query (b, s),
+// s < count_rows[b], sees cache rows <= pos_rows[b] + s; slots s >= count_rows[b] of `out` are not written (count 0: the whole
+// entry).  max_end: the host's bound of pos_rows[b] + count_rows[b] (<= Tmax) -- the 32-bit-offset check uses it and the kernel
+// clamps to it.  Refusals as above.
+int awq_prefill_attention_rows(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
+                               const int32_t* pos_rows, const int32_t* count_rows, int64_t max_end_, int64_t B_, int64_t S_, int64_t Hq_,
+                               int64_t Hkv_, int64_t head_dim, int64_t Tmax_, float scale, float softcap, const float* alibi_slopes,
+                               void* stream) {
+    if (B_ < 0 || S_ < 0 || Hq_ <= 0 || Hkv_ <= 0 || max_end_ < 0 || Tmax_ < 0 || B_ > INT32_MAX || S_ > INT32_MAX || Hq_ > 65535 ||
+        Hkv_ > 65535 || Tmax_ > INT32_MAX || max_end_ > INT32_MAX)
+        return AWQ_ERR_BAD_SHAPE;
+    const int B = (int)B_, S = (int)S_, Hq = (int)Hq_, Hkv = (int)Hkv_, Tmax = (int)Tmax_, max_end = (int)max_end_;
+    if (!q || !k_cache || !v_cache || !out || !pos_rows || !count_rows) return AWQ_ERR_NULL;
+    if (max_end > Tmax) return AWQ_ERR_BAD_SHAPE;
+    if (head_dim != HD || Hq % Hkv) return AWQ_ERR_UNSUPPORTED;
+    if (((uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out) & 15) return AWQ_ERR_BAD_ALIGNMENT;
+    if (((uintptr_t)pos_rows | (uintptr_t)count_rows) & 3) return AWQ_ERR_BAD_ALIGNMENT;
+    if (B == 0 || S == 0 || max_end == 0) return AWQ_OK;
+    if ((uint64_t)S * Hq * HD * 2 >= (1ull << 31) || (uint64_t)max_end * Hkv * HD * 2 >= (1ull << 31)) return AWQ_ERR_UNSUPPORTED;
+    PrefillAttnParams p;
+    p.q = reinterpret_cast<const half_t*>(q);
+    p.k = reinterpret_cast<const half_t*>(k_cache);
+    p.v = reinterpret_cast<const half_t*>(v_cache);
+    p.out = reinterpret_cast<half_t*>(out);
+    p.alibi = alibi_slopes;
+    p.B = B; p.S = S; p.Hq = Hq; p.Hkv = Hkv; p.Tmax = Tmax; p.start = 0;
+    p.pos_rows = pos_rows;
+    p.count_rows = count_rows;
+    p.max_end = max_end;
+    return launch_prefill_attn<true>(p, scale, softcap, stream);
 }

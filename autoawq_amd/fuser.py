@@ -36,6 +36,12 @@ class FusedCausalLM(nn.Module):
         """[B, T] ids -> [B, T, vocab]: the verify step of speculative decoding (LlamaLikeModel.forward(verify=True))"""
         return self.lm_head(self.model(input_ids, verify=True).last_hidden_state)
 
+    @torch.inference_mode()
+    def extend(self, input_ids, pos_rows, count_rows, max_end):
+        """[B, S] ids -> [B, S, vocab]: prefill at per-row positions -- row b's first count_rows[b] ids at positions pos_rows[b] ..
+        (int32 [B] on the device; max_end: the host's bound of their sums), LlamaLikeModel.forward(extend=...)"""
+        return self.lm_head(self.model(input_ids, extend=(pos_rows, count_rows, max_end)).last_hidden_state)
+
 
 def _layout_of(model):
     kinds = {type(m) for m in model.modules() if isinstance(m, (WQLinear_GEMM, WQLinear_GEMV))}

@@ -24,7 +24,10 @@ MI355X-first differences:
     include/awq_hip.h); appends and decode attention run the *_fp8 kernels.  Prefill appends in fp8, dequantizes rows
     [0, start_pos + S) into an fp16 workspace and runs the unchanged prefill attention on it, so a prompt attends to the same
     quantized values its decode steps will read.  Only the native head shapes take it (head_dim 128, 1 / 2 / 4 / 8 query heads per
-    KV head): other shapes slice the cache in torch and are refused at construction."""
+    KV head): other shapes slice the cache in torch and are refused at construction.
+  * `extend_rows = (pos_rows, count_rows, max_end)` (set by the caller, like `verify_rows`): prefill at per-row positions -- a
+    second turn of a conversation, a new prompt in a finished row's slot.  Append with per-row counts, then
+    `awq_prefill_attention_rows`; no reference counterpart (its prefill ignores the cache)."""
 import math
 import os
 
@@ -133,6 +136,7 @@ class QuantAttentionFused(nn.Module):
         self._len_dev = None
         self._per_row = False
         self.verify_rows = False  # set by the caller of a speculative verify step (LlamaLikeModel.forward(verify=True))
+        self.extend_rows = None   # (pos_rows, count_rows, max_end): set by the caller of an extend step (forward(extend=...))
 
     def use_device_positions(self, pos_dev, len_dev, per_row=False):
         """pos_dev / len_dev: int32 device tensors of one element (shared by all layers) holding the
@@ -219,6 +223,36 @@ class QuantAttentionFused(nn.Module):
         attn_output = self.o_proj(heads) if apply_o_proj else heads
         return attn_output, heads, [torch.zeros(1, 1, self.start_pos, 1)]
 
+    def _extend_qkv(self, xqkv, apply_o_proj):
+        """Prefill at per-row positions (asked for explicitly through `extend_rows` = (pos_rows, count_rows, max_end), never
+        inferred from seqlen): sequence b's first count_rows[b] tokens are appended at cache rows pos_rows[b] .. and query (b, s)
+        attends over rows <= pos_rows[b] + s (ops.prefill_attention_rows); the slots behind them write nothing and their output
+        is zeros.  max_end is the host's bound of pos_rows[b] + count_rows[b].  An fp8 cache appends codes, dequantizes rows
+        [0, max_end) and attends over those, as the shared prefill does.  The host-side start_pos is not advanced: the caller
+        owns the positions."""
+        bsz, seqlen, _ = xqkv.shape
+        pos_rows, count_rows, max_end = self.extend_rows
+        max_end = int(max_end)
+        if not (self.head_dim == 128 and self.n_kv_groups in (1, 2, 4, 8)):
+            raise NotImplementedError("an extend step takes head_dim 128 and 1, 2, 4 or 8 query heads per KV head")
+        if not 0 <= max_end <= self.max_seq_len:
+            raise ValueError(f"extend: max_end {max_end} outside the cache window {self.max_seq_len}")
+        xq = ops.rope_kv_append(xqkv, self.cache.k, self.cache.v, self.rope.cos, self.rope.sin, 0, self.n_heads, self.n_kv_heads,
+                                self.head_dim, self.rotary_dim, pos_rows=pos_rows, k_scale=self.cache.k_scale,
+                                v_scale=self.cache.v_scale, count_rows=count_rows)
+        k_rows, v_rows = self.cache.k, self.cache.v
+        if self.kv_cache_dtype == "fp8" and max_end > 0:
+            k_rows = ops.kv_dequant_fp8(self.cache.k, self.cache.k_scale, max_end, bsz)
+            v_rows = ops.kv_dequant_fp8(self.cache.v, self.cache.v_scale, max_end, bsz)
+        if max_end == 0:  # no row has a token and none a context: nothing to attend
+            out = torch.zeros_like(xq)
+        else:
+            out = ops.prefill_attention_rows(xq, k_rows, v_rows, pos_rows, count_rows, max_end, softcap=self.attn_logit_softcapping,
+                                             alibi_slopes=self.alibi.slopes if self.alibi is not None else None)
+        heads = out.reshape(bsz, seqlen, -1)
+        attn_output = self.o_proj(heads) if apply_o_proj else heads
+        return attn_output, heads, [torch.zeros(1, 1, self.start_pos, 1)]
+
     def forward_qkv(self, xqkv, apply_o_proj=True):
         """Everything after the qkv projection (the caller may have produced `xqkv` [B, S, (Hq + 2 Hkv) D]
         with the norm folded into the projection).  apply_o_proj=False returns the attention heads' output
@@ -228,6 +262,8 @@ class QuantAttentionFused(nn.Module):
         xqkv = self._qkv_rows(xqkv)
         if self.verify_rows:
             return self._verify_qkv(xqkv, apply_o_proj)
+        if self.extend_rows is not None:
+            return self._extend_qkv(xqkv, apply_o_proj)
         device_pos = self._pos_dev is not None and seqlen == 1
         rows = device_pos and self._per_row  # one position / length word per sequence: the *_rows kernels
         # the hand-written decode kernels take head_dim 128 and 1, 2, 4 or 8 query heads per KV head; other

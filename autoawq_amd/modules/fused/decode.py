@@ -50,13 +50,22 @@ drafts of their own.  draft_tokens=0 (the default) creates none of this.
 
     out = dec.generate(ids, max_new_tokens=128, draft_tokens=3, draft_ngram=3)   # the text of the plain greedy run
     dec.last_spec                                                                 # {"replays": r, "new_tokens": [n_b ...]}
+
+Prefill at per-row positions (`extend`, `reset_rows`, `generate(extend=True)`): eager, no graph family.  `extend` appends row b's
+tokens at ITS position (rope + append with per-row counts, then csrc/prefill_attn.hip's rows form) and leaves the decoder in
+per-row mode; a row with an all-zero mask is untouched.  `reset_rows` sends rows back to position 0 and keeps the others: a
+finished row's slot takes a new prompt while its neighbours go on.  `generate` records what it left in the caches per row (`tail`:
+modules/fused/ragged.py, generate_tail), and a following `generate(extend=True)` continues from there instead of restarting.
+
+    out1 = dec.generate(turn1, max_new_tokens=64, eos_token_id=eos)
+    out2 = dec.generate(turn2, max_new_tokens=64, eos_token_id=eos, extend=True)   # turn 1 is not prefilled again
 """
 import torch
 
 from ... import ops
 from ..._lib import AwqHipError
 from .model import StepPlan
-from .ragged import mask_runs, pack_ids, unpack_rows
+from .ragged import generate_tail, mask_runs, mask_runs_extend, pack_ids, unpack_rows
 
 
 class GraphedDecoder:
@@ -104,6 +113,7 @@ class GraphedDecoder:
         self._spec = {}          # T -> the device words of the speculative path (allocated by its first use)
         self._verify_T = None    # tokens appended by the last `verify`, until `advance_rows`
         self.last_spec = None
+        self.tail = None         # what the last plain `generate` left per row: {"cache_rows": [...], "pending": [...]} (generate_tail)
         self.position = 0
         self.positions = None  # per-row mode: the host's position of every row (None: one shared position)
         for b in self.blocks:
@@ -120,10 +130,12 @@ class GraphedDecoder:
         self.lm.model.last_forward_num_tokens = self.position
 
     def seek(self, position):
-        """Declare that `position` cache rows are valid (benchmarks and tests that fill the caches themselves)."""
+        """Declare that `position` cache rows are valid (benchmarks and tests that fill the caches themselves).  Like every
+        other move of the positions from outside `generate`, it drops `tail`."""
         if not 0 <= position <= self.max_seq_len:  # (== max_seq_len: a full window -- the next step rolls it first)
             raise ValueError(f"position {position} outside the cache window {self.max_seq_len}")
         self.positions = None
+        self.tail = None
         self.position = int(position)
         self.pos.fill_(self.position)
         self.len.fill_(self.position + 1)
@@ -137,6 +149,7 @@ class GraphedDecoder:
         if not all(0 <= p <= self.max_seq_len for p in positions):
             raise ValueError(f"seek_rows: positions {positions} outside the cache window {self.max_seq_len}")
         self.positions = positions
+        self.tail = None
         p = torch.tensor(positions, dtype=torch.int32)
         self.pos_rows.copy_(p)
         self.len_rows.copy_(p + 1)
@@ -183,6 +196,90 @@ class GraphedDecoder:
         logits = self._prefill_eager(pack_ids(input_ids, starts, lengths))  # [B, max L_b, V]: row b's tokens at 0 .. L_b - 1
         self.seek_rows(lengths)
         return unpack_rows(logits, starts, lengths, input_ids.shape[1])
+
+    # ---- prefill at per-row positions: eager ---------------------------------------------------------------------------------
+    def _row_positions(self):
+        return list(self.positions) if self.positions is not None else [self.position] * self.batch
+
+    def _extend_packed(self, packed, base, lengths):
+        """packed [B, W] ids, row b's lengths[b] tokens at columns 0 ..: appended at positions base[b] ..  Returns the logits
+        [B, W, V] and leaves the decoder in per-row mode at base[b] + lengths[b]."""
+        ends = [p + n for p, n in zip(base, lengths)]
+        if max(ends) > self.max_seq_len:  # before any launch
+            raise ValueError(f"extend: positions {base} + {lengths} tokens run past the cache window {self.max_seq_len} "
+                             "(extend never rolls the window)")
+        pos = torch.tensor(base, dtype=torch.int32).to(self.device)
+        cnt = torch.tensor(lengths, dtype=torch.int32).to(self.device)
+        logits = self.lm.extend(packed, pos, cnt, max(ends))
+        self.seek_rows(ends)
+        return logits
+
+    @torch.inference_mode()
+    def extend(self, input_ids, attention_mask=None):
+        """input_ids [B, S] -> logits [B, S, vocab], eager: `prefill` that continues.  Row b's L_b >= 0 real tokens (attention_mask as
+        in `prefill`, but a row may be all zeros; no mask: L_b = S) take positions p_b .. p_b + L_b - 1, p_b the row's current
+        position (shared mode: `position` for every row); what the row has cached below p_b stays and is attended to.  A row
+        with L_b = 0 is untouched.  Afterwards the decoder is in per-row mode at p_b + L_b.  The logits come back in the
+        caller's layout; the values at pad columns are unspecified.  p_b + L_b > max_seq_len raises ValueError: extend never
+        rolls the window."""
+        input_ids = input_ids.to(self.device)
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
+            raise ValueError(f"input_ids must be [{self.batch}, tokens], got {tuple(input_ids.shape)}")
+        S = input_ids.shape[1]
+        if attention_mask is None:
+            starts, lengths = [0] * self.batch, [S] * self.batch
+        else:
+            starts, lengths = mask_runs_extend(attention_mask, input_ids.shape)
+        base = self._row_positions()
+        if S == 0:
+            self.seek_rows(base)
+            return torch.zeros((self.batch, 0, int(self.lm.model.vocab_size)), dtype=torch.float16, device=self.device)
+        # (a row without tokens is packed as if it had one: its count stays 0, so nothing of it is appended or attended)
+        logits = self._extend_packed(pack_ids(input_ids, starts, [max(n, 1) for n in lengths]), base, lengths)
+        return unpack_rows(logits, starts, lengths, S)
+
+    def reset_rows(self, rows):
+        """The rows listed go back to position 0 and the others keep theirs (per-row mode from here on).  Nothing is cleared:
+        cache rows at and above a row's position are dead by construction.  A following `extend` with a mask that is zero in the
+        other rows puts a new prompt into these slots."""
+        rows = [int(r) for r in rows]
+        if not all(0 <= r < self.batch for r in rows):
+            raise ValueError(f"reset_rows: rows {rows} outside the batch of {self.batch}")
+        base = self._row_positions()
+        for r in rows:
+            base[r] = 0
+        tail = self.tail
+        self.seek_rows(base)
+        if tail is not None:  # the other rows still owe their last token
+            for r in rows:
+                tail["cache_rows"][r], tail["pending"][r] = 0, None
+            self.tail = tail
+
+    def _extend_turn(self, input_ids, attention_mask):
+        """generate(extend=True) up to token 1's logits: every row goes back to what the last generate left in its cache (`tail`),
+        the token that call emitted last and never fed is put in front of the row's new tokens, and the lot is extended.
+        Returns (logits [B, 1, V] at every row's last new position, the rows with nothing to process)."""
+        B, S = input_ids.shape
+        if attention_mask is None:
+            starts, lengths = [0] * B, [S] * B
+        else:
+            starts, lengths = mask_runs_extend(attention_mask, input_ids.shape)
+        tail = self.tail if self.tail is not None else {"cache_rows": self._row_positions(), "pending": [None] * B}
+        rows = []
+        for b in range(B):
+            new = input_ids[b, starts[b]:starts[b] + lengths[b]].long()
+            if tail["pending"][b] is not None:
+                new = torch.cat([torch.tensor([tail["pending"][b]], dtype=torch.int64, device=new.device), new])
+            rows.append(new)
+        counts = [int(r.numel()) for r in rows]
+        idle = [b for b, n in enumerate(counts) if n == 0]
+        width = max(max(counts), 1)
+        packed = torch.zeros((B, width), dtype=torch.int64, device=self.device)
+        for b, r in enumerate(rows):
+            packed[b, :counts[b]] = r
+        logits = self._extend_packed(packed, list(tail["cache_rows"]), counts)
+        last = torch.tensor([max(n - 1, 0) for n in counts], dtype=torch.int64, device=self.device)
+        return logits[torch.arange(B, device=self.device), last].unsqueeze(1).contiguous(), idle
 
     # ---- one token ------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
@@ -235,6 +332,7 @@ class GraphedDecoder:
         """What `step` and `replay` share: roll a full window, pick (or capture) the bucket's graph, replay it on the decoder's stream
         between the caller's work, advance the position on the host as the graph did on the device.  greedy = True / False:
         the generation graph (step + sampler) instead of the step graph; proc: the one whose sampler runs the logit processors."""
+        self.tail = None  # (generate states it again when it is done)
         if self.positions is not None:
             return self._advance_rows(greedy, proc)
         if self.position + 1 > self.max_seq_len:  # past the window: forget the oldest positions (eagerly)
@@ -517,7 +615,7 @@ class GraphedDecoder:
     @torch.inference_mode()
     def generate(self, input_ids, max_new_tokens, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                  eos_token_id=None, pad_token_id=None, check_every=16, attention_mask=None, repetition_penalty=1.0,
-                 min_new_tokens=0, draft_tokens=0, draft_ngram=3):
+                 min_new_tokens=0, draft_tokens=0, draft_ngram=3, extend=False):
         """input_ids [batch, prompt] -> [batch, prompt + n] int64 on the device, n <= max_new_tokens; rows that emitted an EOS id
         are padded with pad_token_id (default: the first EOS id) from then on, and the run stops once every row has (HF's
         `generate` semantics).  The prompt is prefilled eagerly and token 1 sampled eagerly from its last position; every later
@@ -536,7 +634,13 @@ class GraphedDecoder:
         earlier in its own text and emits 1 .. K + 1 tokens; the text is the plain greedy run's (up to ties the two launch shapes
         round differently).  `last_spec` then holds {"replays": those the slowest row needed, "new_tokens": per row, "launched"}.  Greedy only (do_sample with temperature > 0,
         repetition_penalty != 1 and min_new_tokens > 0 raise ValueError; an fp8 cache NotImplementedError), and no window roll:
-        prompt + max_new_tokens + K + 1 <= max_seq_len for every row."""
+        prompt + max_new_tokens + K + 1 <= max_seq_len for every row.
+        extend=True: input_ids / attention_mask (a row may be all zeros) are APPENDED to each row's context instead of
+        restarting it -- the next turn of a conversation.  Every row goes back to what the previous call left in its cache
+        (`tail`: its prompt and the real tokens it was fed; the pads fed to a finished row are dropped), the last token that call
+        emitted without feeding it comes first, then the new tokens, in one `extend`.  A row with neither starts finished and
+        emits pads.  The repetition-penalty history is kept and extended by the new ids.  Not with draft_tokens (ValueError);
+        the window is `extend`'s: no roll while the new tokens are appended."""
         input_ids = input_ids.to(self.device)
         if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
             raise ValueError(f"input_ids must be [{self.batch}, prompt], got {tuple(input_ids.shape)}")
@@ -544,6 +648,8 @@ class GraphedDecoder:
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         eos = [] if eos_token_id is None else ([int(eos_token_id)] if isinstance(eos_token_id, int) else [int(e) for e in eos_token_id])
+        if draft_tokens and extend:
+            raise ValueError("generate(extend=True) does not take draft_tokens: the speculative path keeps no history across calls")
         if draft_tokens:
             if isinstance(draft_tokens, bool) or int(draft_tokens) != draft_tokens or not 1 <= int(draft_tokens) <= 7:
                 raise ValueError(f"draft_tokens must be an integer in 0 .. 7, got {draft_tokens}")
@@ -558,21 +664,31 @@ class GraphedDecoder:
         proc_bytes = ops.sample_proc_params(repetition_penalty, min_new_tokens)
         proc = float(repetition_penalty) != 1.0 or int(min_new_tokens) > 0
         greedy = not do_sample or float(temperature) <= 0
-        ragged = self._ragged(input_ids, attention_mask)
-        logits = self.prefill(input_ids, attention_mask if ragged is not None else None)
-        if ragged is not None:  # the first token of row b comes from its column start_b + L_b - 1
-            last = torch.tensor([s + n - 1 for s, n in zip(*ragged)], dtype=torch.int64, device=self.device)
-            logits = logits[torch.arange(self.batch, device=self.device), last].unsqueeze(1).contiguous()
+        idle = []
+        if extend:
+            logits, idle = self._extend_turn(input_ids, attention_mask)
+        else:
+            ragged = self._ragged(input_ids, attention_mask)
+            logits = self.prefill(input_ids, attention_mask if ragged is not None else None)
+            if ragged is not None:  # the first token of row b comes from its column start_b + L_b - 1
+                last = torch.tensor([s + n - 1 for s, n in zip(*ragged)], dtype=torch.int64, device=self.device)
+                logits = logits[torch.arange(self.batch, device=self.device), last].unsqueeze(1).contiguous()
+        before = self._gen
         g = self._gen_state(logits.shape[-1], max_new_tokens)
         # reset every decoder-owned device word, outside any capture
         g["params"].copy_(params)
         g["t"].fill_(1)
         g["ring"].zero_()
         g["finished"].zero_()
+        if idle:  # nothing to process: the row starts finished and emits pads
+            g["finished"][torch.tensor(idle, device=self.device)] = 1
         g["status"].zero_()
         if proc:
             g["proc"].copy_(proc_bytes)
-            g["history"].zero_()
+            if not extend:
+                g["history"].zero_()
+            elif before is not None and before is not g and before["vocab"] == g["vocab"]:
+                g["history"].copy_(before["history"])  # the words were reallocated (a longer ring): the ids seen so far move along
             ops.sample_history(input_ids, g["vocab"], out=g["history"])
         self._sample(logits, greedy, proc)  # token 1, eagerly, into self.tok
         n = 1
@@ -583,6 +699,11 @@ class GraphedDecoder:
             n += 1
         done = self._check(g)
         new = g["ring"][:, :n]
+        # what this call leaves in the caches, for a following generate(extend=True).  n - 1 tokens were fed since token 1 was
+        # sampled: counted back from where the rows stand now, a window roll in between is accounted for
+        lengths = [p - (n - 1) for p in self._row_positions()]
+        cache_rows, pending = generate_tail(lengths, new.cpu().tolist(), eos, n, idle=idle)
+        self.tail = {"cache_rows": cache_rows, "pending": pending}
         if done and eos:  # HF stops at the step where the last row finished: drop the all-pad columns after it
             hit = torch.zeros_like(new, dtype=torch.bool)
             for e in eos:

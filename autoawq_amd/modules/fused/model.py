@@ -80,11 +80,21 @@ class LlamaLikeModel(nn.Module):
                         and isinstance(b.norm_2, FasterTransformerRMSNorm) for b in self.blocks))
 
     @torch.inference_mode()
-    def forward(self, input_ids, *args, verify=False, **kwargs):
+    def forward(self, input_ids, *args, verify=False, extend=None, **kwargs):
         """verify=True: the T-token verify step of speculative decoding (modules/fused/decode.py).  [B, T] ids at the per-row
         device positions the caller has set on the blocks: no StepPlan -- nothing cached is forgotten, no id is sliced away --
         and neither `last_forward_num_tokens` nor the blocks' start_pos move; the caller advances its positions by what it
-        accepts and restates the host bookkeeping (GraphedDecoder._sync_host_state)."""
+        accepts and restates the host bookkeeping (GraphedDecoder._sync_host_state).
+        extend=(pos_rows, count_rows, max_end): prefill at per-row positions (QuantAttentionFused._extend_qkv) -- [B, S] ids, row
+        b's first count_rows[b] at positions pos_rows[b] ..; the same bookkeeping rules as verify."""
+        if extend is not None:
+            for b in self.blocks:
+                b.attn.extend_rows = tuple(extend)
+            try:
+                return self._run_blocks(input_ids)
+            finally:
+                for b in self.blocks:
+                    b.attn.extend_rows = None
         if verify:
             for b in self.blocks:
                 b.attn.verify_rows = True

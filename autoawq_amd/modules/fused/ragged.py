@@ -38,6 +38,53 @@ def mask_runs(attention_mask, shape, max_len=None):
     return starts, lens
 
 
+def mask_runs_extend(attention_mask, shape):
+    """`mask_runs` for GraphedDecoder.extend, where a row may bring no token at all: an all-zero row is (start 0, length 0).
+    Everything else is refused as there (shape, values other than 0 / 1, ones that are not one contiguous run); the window
+    is the caller's check -- it depends on where each row stands."""
+    m = torch.as_tensor(attention_mask)
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError(f"attention_mask has shape {tuple(m.shape)}, input_ids {tuple(shape)}")
+    m = m.detach().to("cpu")
+    if m.dtype.is_floating_point or m.dtype.is_complex:
+        raise ValueError("attention_mask must hold integers (0 / 1) or booleans")
+    m = m.to(torch.int64)
+    if bool(((m != 0) & (m != 1)).any()):
+        raise ValueError("attention_mask must hold only 0 and 1")
+    starts, lens = [], []
+    for b in range(m.shape[0]):
+        n = int(m[b].sum())
+        s = int(m[b].argmax()) if n else 0
+        if int(m[b, s:s + n].sum()) != n:
+            raise ValueError(f"attention_mask row {b}: the ones must form one contiguous run (left or right padding)")
+        starts.append(s)
+        lens.append(n)
+    return starts, lens
+
+
+def generate_tail(lengths, ring, eos, n, idle=()):
+    """What a `generate` call leaves behind, per row: (cache_rows, pending).  lengths[b]: the cache rows of row b when token 1
+    was sampled (its prompt); ring[b][:n]: the n tokens the call sampled for it -- the row's real tokens up to and including its
+    first EOS id, pads from then on; rows in `idle` started finished and emitted pads only.  Token i + 1 is sampled by the step
+    that feeds token i, so ring[b][:n - 1] were fed (appended to the cache, real tokens and pads alike) and ring[b][n - 1] was not.
+      cache_rows[b] = lengths[b] + the real tokens that were fed: the rows above hold pads and are dead;
+      pending[b]    = the last real token if it was not fed (the row never finished, or finished on token n), else None.
+    Pure host code: lists or a CPU tensor in, two lists out."""
+    eos = set(int(e) for e in eos)
+    cache_rows, pending = [], []
+    for b, L in enumerate(lengths):
+        row = [int(t) for t in ring[b][:n]]
+        if len(row) != n or n < 1:
+            raise ValueError(f"generate_tail: row {b} of the ring holds {len(row)} tokens, n = {n}")
+        if b in idle:
+            real = 0
+        else:
+            real = next((i + 1 for i, t in enumerate(row) if t in eos), n)
+        cache_rows.append(int(L) + min(real, n - 1))
+        pending.append(row[n - 1] if real == n else None)
+    return cache_rows, pending
+
+
 def _columns(starts, lengths, width, device):
     """[B, width] source column of each packed column: start_b + min(i, L_b - 1)"""
     i = torch.arange(width, device=device).view(1, -1)

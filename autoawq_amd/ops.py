@@ -721,11 +721,13 @@ def _stream_workspace(table, device, need):
 
 
 def rope_kv_append(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n_kv_heads, head_dim, rotary_dim, pos_dev=None,
-                   pos_rows=None, k_scale=None, v_scale=None):
+                   pos_rows=None, k_scale=None, v_scale=None, count_rows=None):
     """qkv [B, S, (Hq + 2 Hkv) * D] fp16 -> rotated q [B, S, Hq, D]; rotated k and v are written into
     the caches [B, Tmax, Hkv, D] at rows start_pos .. start_pos + S - 1 (awq_rope_kv_append).  pos_rows (int32 [B] on the
     device; start_pos is then ignored): sequence b starts at pos_rows[b] (awq_rope_kv_append_rows).  k_scale / v_scale
-    ([B, Tmax, Hkv] fp32) with uint8 caches: the fp8 cache -- rows are stored as e4m3 codes + scales (awq_rope_kv_append*_fp8)."""
+    ([B, Tmax, Hkv] fp32) with uint8 caches: the fp8 cache -- rows are stored as e4m3 codes + scales (awq_rope_kv_append*_fp8).
+    count_rows (int32 [B] on the device, with pos_rows): sequence b has count_rows[b] new tokens; the slots behind them write
+    nothing to the caches and their q is unspecified (awq_rope_kv_append_rows_n*)."""
     kv8 = _kv8("rope_kv_append", k_cache, v_cache, k_scale, v_scale)
     _require_gpu(qkv, k_cache, v_cache, cos, sin, pos_dev, pos_rows, k_scale, v_scale)
     B, S = qkv.shape[0], qkv.shape[1]
@@ -736,11 +738,16 @@ def rope_kv_append(qkv, k_cache, v_cache, cos, sin, start_pos, n_heads, n_kv_hea
     rows = pos_rows is not None
     if rows:
         _check_rows("rope_kv_append", "pos", pos_rows, pos_dev, B, qkv.device)
-    name = "awq_rope_kv_append" + ("_rows" if rows else "") + ("_fp8" if kv8 else "")
+    counts = count_rows is not None
+    if counts:
+        if not rows:
+            raise _lib.AwqHipError("rope_kv_append: count_rows goes with pos_rows")
+        _check_rows("rope_kv_append", "count", count_rows, None, B, qkv.device)
+    name = "awq_rope_kv_append" + ("_rows" if rows else "") + ("_n" if counts else "") + ("_fp8" if kv8 else "")
     with torch.cuda.device(qkv.device):
         _lib.check(getattr(_lib.lib(), name)(
             _ptr(qkv), _ptr(q), *_kv_ptrs(kv8, k_cache, v_cache, k_scale, v_scale), _ptr(cos), _ptr(sin),
-            *([_ptr(pos_rows)] if rows else [_ptr(pos_dev), int(start_pos)]),
+            *([_ptr(pos_rows)] + ([_ptr(count_rows)] if counts else []) if rows else [_ptr(pos_dev), int(start_pos)]),
             B, S, n_heads, n_kv_heads, head_dim, rotary_dim, k_cache.shape[1], _stream()), name)
     return q
 
@@ -767,6 +774,37 @@ def prefill_attention(q, k_cache, v_cache, start_pos, scale=None, softcap=0.0, a
     with torch.cuda.device(q.device):
         _lib.check(_lib.lib().awq_prefill_attention(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), B, S, Hq, Hkv, D, Tmax, int(start_pos),
                                                     float(scale), float(softcap), _ptr(alibi_slopes), _stream()), "awq_prefill_attention")
+    return out
+
+
+def prefill_attention_rows(q, k_cache, v_cache, pos_rows, count_rows, max_end, scale=None, softcap=0.0, alibi_slopes=None, out=None):
+    """prefill_attention with one start and one count per sequence (int32 [B] on the device): query (b, s), s < count_rows[b],
+    sees cache rows <= pos_rows[b] + s; the slots behind them are not written -- `out` (default: zeros) keeps what it held
+    there.  max_end: the host's bound of pos_rows[b] + count_rows[b], <= Tmax (awq_prefill_attention_rows)."""
+    _require_gpu(q, k_cache, v_cache, alibi_slopes, pos_rows, count_rows, out)
+    if q.dtype != torch.float16 or k_cache.dtype != torch.float16 or v_cache.dtype != torch.float16:
+        raise _lib.AwqHipError("prefill_attention_rows expects fp16 tensors")
+    B, S, Hq, D = q.shape
+    Tmax, Hkv = k_cache.shape[1], k_cache.shape[2]
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()) or k_cache.shape[0] < B or k_cache.shape != v_cache.shape:
+        raise _lib.AwqHipError("prefill_attention_rows: caches must be contiguous [>=B, Tmax, Hkv, D]")
+    _check_rows("prefill_attention_rows", "pos", pos_rows, None, B, q.device)
+    _check_rows("prefill_attention_rows", "count", count_rows, None, B, q.device)
+    q = q.contiguous()
+    if out is None:
+        out = torch.zeros_like(q)
+    elif out.shape != q.shape or out.dtype != q.dtype or not out.is_contiguous():
+        raise _lib.AwqHipError("prefill_attention_rows: out must be a contiguous fp16 tensor of q's shape")
+    if alibi_slopes is not None:
+        alibi_slopes = alibi_slopes.to(torch.float32).contiguous()
+        if alibi_slopes.numel() != Hq:
+            raise _lib.AwqHipError("prefill_attention_rows: alibi_slopes must have one entry per query head")
+    if scale is None:
+        scale = D ** -0.5
+    with torch.cuda.device(q.device):
+        _lib.check(_lib.lib().awq_prefill_attention_rows(_ptr(q), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos_rows),
+                                                         _ptr(count_rows), int(max_end), B, S, Hq, Hkv, D, Tmax, float(scale),
+                                                         float(softcap), _ptr(alibi_slopes), _stream()), "awq_prefill_attention_rows")
     return out
 
 

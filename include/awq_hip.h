@@ -526,6 +526,36 @@ AWQ_EXPORT int awq_kv_quant_fp8(const uint16_t* x, uint8_t* cache, float* scales
 AWQ_EXPORT int awq_kv_dequant_fp8(const uint8_t* cache, const float* scales, uint16_t* out, int64_t B, int64_t n,
                                   int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, void* stream);
 
+/* ---- prefill at per-row positions (GraphedDecoder.extend: a second turn, a refilled slot) ---------------------------------
+ * The prefill step with one start AND one token count per sequence, read on the device from int32 arrays of B words (never NULL).
+ * No reference counterpart: its prefill ignores the cache and restarts at 0 (attn.py:269-277).
+ *   awq_rope_kv_append_rows_n[_fp8]: awq_rope_kv_append_rows[_fp8] for the slots s < count_rows[b] of sequence b -- same rows, same
+ *                                    bits; slots s >= count_rows[b] write nothing to the caches or the scales (their q_out is
+ *                                    unspecified).  The plain rows form clamps to row max_seq - 1: a pad slot of a sequence whose
+ *                                    tokens end exactly at max_seq would overwrite its last real row.
+ *   awq_prefill_attention_rows:      q / out [B, S, n_heads, 128] fp16, caches [>= B, max_seq, n_kv_heads, 128] fp16 holding rows
+ *                                    0 .. pos_rows[b] + count_rows[b] - 1 of sequence b.  Query (b, s) with s < count_rows[b] sees
+ *                                    cache rows <= pos_rows[b] + s; slots s >= count_rows[b] of `out` are NOT written
+ *                                    (count_rows[b] == 0: the whole sequence).  max_end is the host's bound of pos_rows[b] +
+ *                                    count_rows[b], <= max_seq: the 32-bit-offset check uses it and the kernel clamps both words to
+ *                                    it.  scale / softcap / alibi_slopes and the refusals as in awq_prefill_attention; the same
+ *                                    tile walk, so with pos_rows[b] = start and count_rows[b] = S for every b the result is
+ *                                    bit-identical to awq_prefill_attention(start).
+ * An fp8 cache has no attention kernel of its own: dequantise rows [0, max_end) with awq_kv_dequant_fp8 and attend over that. */
+AWQ_EXPORT int awq_rope_kv_append_rows_n(const uint16_t* qkv, uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache,
+                                         const float* cos_table, const float* sin_table, const int32_t* pos_rows,
+                                         const int32_t* count_rows, int64_t B, int64_t S, int64_t n_heads, int64_t n_kv_heads,
+                                         int64_t head_dim, int64_t rotary_dim, int64_t max_seq, void* stream);
+AWQ_EXPORT int awq_rope_kv_append_rows_n_fp8(const uint16_t* qkv, uint16_t* q_out, uint8_t* k_cache, uint8_t* v_cache,
+                                             float* k_scale, float* v_scale, const float* cos_table, const float* sin_table,
+                                             const int32_t* pos_rows, const int32_t* count_rows, int64_t B, int64_t S,
+                                             int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t rotary_dim,
+                                             int64_t max_seq, void* stream);
+AWQ_EXPORT int awq_prefill_attention_rows(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, uint16_t* out,
+                                          const int32_t* pos_rows, const int32_t* count_rows, int64_t max_end, int64_t B, int64_t S,
+                                          int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t max_seq, float scale,
+                                          float softcap, const float* alibi_slopes, void* stream);
+
 /* ---- one-shot small-message all-reduce for tensor-parallel decode (no reference counterpart: SURVEY.md 2.3 / 8e) ------
  * out[i] = sum over ranks of in_r[i], fp16 with fp32 accumulation in rank order (bitwise identical on every rank), for the
  * [M, hidden] outputs of row-parallel projections (n_halfs % 4 == 0, n_halfs <= max_halfs; <= 64 KiB is what it is built for).
