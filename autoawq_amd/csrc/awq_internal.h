@@ -44,7 +44,7 @@ struct AwqGemmArgs {
     const int32_t* qweight;  // [K, N/8]
     const uint16_t* scales;  // [K/g, N]
     const int32_t* qzeros;   // [K/g, N/8]
-    const uint16_t* bias;    // [N] or null
+    const uint16_t* bias = nullptr;  // [N] or null
     uint16_t* y;             // [M, N]
     int M, K, N, g;
     int x_gated = 0;  // decode kernel only: 1 = x is [M, 2K] = [gate | up], stage silu(gate) * up; 2 = stage rmsnorm(x + res_in)
@@ -56,12 +56,28 @@ struct AwqGemmArgs {
     int ssq_in_tiles = 0;
     const uint16_t* add_res = nullptr;  // epilogue (decode kernel, M <= 4): y = fp16(fp16(x W + bias) + add_res)
     float* ssq_out = nullptr;           // epilogue: [M, ceil(N / 256)] sums of squares of y per 256-column tile
-    int* counters;   // control words (word 0 = error flag), zero on entry
-    float* exchange;  // in-launch split-K exchange region: all-ones sentinel on entry AND on exit
-    size_t exchange_bytes;
-    float* partial;  // scratch fp32 slabs for the two-pass reducers (no invariant between calls)
-    size_t partial_floats;
+    // the workspace (none unless capi.hip carves one):
+    int* counters = nullptr;    // control words (word 0 = error flag), zero on entry
+    float* exchange = nullptr;  // in-launch split-K exchange region: all-ones sentinel on entry AND on exit
+    size_t exchange_bytes = 0;
+    float* partial = nullptr;   // scratch fp32 slabs for the two-pass reducers (no invariant between calls)
+    size_t partial_floats = 0;
     hipStream_t stream;
+};
+
+// The routing of a grouped (MoE) launch over stacked expert tensors, beside the AwqGemmArgs of one expert's product.
+struct AwqGroupedArgs {
+    const float* pair_weights = nullptr;  // [num_pairs] routing weights by pair index, or null
+    int x_div = 1;                        // pair i (a gathered row r: row_map[r]) reads activation row i / x_div
+    // token blocks (awq_launch_grouped_gemm): block b gathers rows sorted_ids[M b .. M b + M - 1] for expert expert_ids[b]
+    const int32_t *sorted_ids = nullptr, *expert_ids = nullptr, *num_post_pad = nullptr;
+    int num_pairs = 0, max_blocks = 0;
+    int64_t expert_qw_words = 0, expert_z_words = 0, expert_s_halfs = 0;  // strides of the expert stacks
+    // rows sorted by expert (awq_launch_gemm_regb_grouped): seg [num_experts + 1] row offsets on the device; row_map / gather /
+    // scatter: see RegbParams (all optional; without row_map the rows of x and y are the sorted rows)
+    const int32_t *seg = nullptr, *row_map = nullptr;
+    int num_experts = 0;
+    bool gather = false, scatter = false;
 };
 
 int awq_launch_gemm_naive(const AwqGemmArgs& a);
@@ -136,18 +152,13 @@ bool awq_gemm_regb_nk_supports(int M, int K, int N, int g, int ZW);
 int awq_launch_gemm_regb_nk(const AwqGemvArgs& a, int bm);
 // GEMM-layout words + the GEMVFast format's scales / fp16 zero terms [>= K/g, N] (gemm_regb.hip, FZ form: W = fp16(w s + qzeros))
 int awq_launch_gemm_regb_fz(const AwqGemvArgs& a, int bm);
-// MoE prefill: the same kernel over a token list sorted by expert (device-side row offsets), GEMM-layout expert stacks
-int awq_launch_gemm_regb_grouped(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
-                                 uint16_t* y, const int32_t* seg, int P, int E, int K, int N, int g, int bm, hipStream_t st,
-                                 const int32_t* row_map = nullptr, int x_div = 1, const float* pair_w = nullptr, int gather = 0,
-                                 int scatter = 0);
+// MoE prefill: the same kernel over a token list sorted by expert (device-side row offsets), GEMM-layout expert stacks; a.M = the pairs
+int awq_launch_gemm_regb_grouped(const AwqGemmArgs& a, const AwqGroupedArgs& r, int bm);
 int awq_launch_moe_sort(const int* ids, int P, int E, int* order, int* seg, hipStream_t st);
 int awq_launch_dequant_nk(const AwqGemvArgs& a);
 // Grouped (MoE) GEMM over stacked expert tensors (awq/modules/fused/moe.py:60-89), M = 16-row token blocks.
 size_t awq_grouped_workspace_bytes_impl(int max_blocks, int K, int N);
-int awq_launch_grouped_gemm(const AwqGemmArgs& a, const int* sorted_ids, const int* expert_ids, const int* num_post_pad,
-                            const float* pair_weights, int num_pairs, int x_div, int max_blocks, int64_t expert_qw_words,
-                            int64_t expert_z_words, int64_t expert_s_halfs);
+int awq_launch_grouped_gemm(const AwqGemmArgs& a, const AwqGroupedArgs& r);
 // out[r, d] = silu(in[r, d]) * in[r, D + d]   (awq_ext.silu_and_mul, moe.py:73-76)
 int awq_launch_silu_and_mul(const uint16_t* in, uint16_t* out, int64_t rows, int64_t D, hipStream_t st);
 // GEMVFast layout (qweight int16 [N/4, K], scales / qzeros fp16 [8*ZW, N], qzeros = -(s*z)).

@@ -2,18 +2,176 @@
 // Validation + kernel selection only; kernels live in the other translation units.
 #include "awq_internal.h"
 
+/* ---- GEMM layout and the MoE grouped GEMMs built on it: an entry point checks what only it takes, calls check_gemm (the shape rule,
+ * the ranges, the five operand pointers and their alignment; it fills the launch's arguments), and launches -- awq_gemm_forward and
+ * its fused forms what gemm_plan names */
 namespace {
 thread_local const char* g_last_kernel = "none";
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-int check_gemm_layout(int64_t K, int64_t N, int64_t g) {
-    // awq/modules/linear/gemm.py:132-133
-    if (K < 0 || N < 0 || g <= 0) return AWQ_ERR_BAD_SHAPE;
-    if (N % 8 != 0) return AWQ_ERR_BAD_SHAPE;
-    if (K % g != 0) return AWQ_ERR_BAD_SHAPE;
-    if (K > INT32_MAX || N > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+// The block tile the NLOG field asks of the LDS-tiled and register-decoded kernels: 2 = 256, 1 = 128 where the entry point takes
+// both (`both`), anything else 0 = the launcher's choice.
+inline int block_width(uint32_t flags, bool both) {
+    const unsigned nlog = AWQ_GEMM_FLAG_NLOG(flags);
+    return nlog == 2 ? 256 : (both && nlog == 1 ? 128 : 0);
+}
+
+// awq/modules/linear/gemm.py:132-133
+bool gemm_layout(int64_t K, int64_t N, int64_t g) { return K >= 0 && N >= 0 && g > 0 && N % 8 == 0 && K % g == 0 && K <= INT32_MAX && N <= INT32_MAX; }
+
+// The layout rule and the range of M; then, unless the call is empty (`empty`: the entry point's own rule -- the caller returns AWQ_OK),
+// the five operand pointers and their 16-byte alignment.  own_range / own_present: the entry point's verdict on the sizes and
+// pointers only it takes (its range checks answer AWQ_ERR_BAD_SHAPE like the rule; what it refuses with AWQ_ERR_UNSUPPORTED comes
+// after).  The one place where the sizes are narrowed and the operands filled: the other fields of *a stay as they are.
+int check_gemm(AwqGemmArgs* a, const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* y,
+               int64_t M, int64_t K, int64_t N, int64_t g, void* stream, bool empty, bool own_range = true, bool own_present = true) {
+    if (!gemm_layout(K, N, g) || M < 0 || M > INT32_MAX || !own_range) return AWQ_ERR_BAD_SHAPE;
+    a->x = x; a->qweight = qweight; a->scales = scales; a->qzeros = qzeros; a->y = y;
+    a->M = (int)M; a->K = (int)K; a->N = (int)N; a->g = (int)g;
+    a->stream = static_cast<hipStream_t>(stream);
+    if (empty) return AWQ_OK;
+    if (!x || !qweight || !scales || !qzeros || !y || !own_present) return AWQ_ERR_NULL;
+    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales) || !aligned16(qzeros) || !aligned16(y)) return AWQ_ERR_BAD_ALIGNMENT;
     return AWQ_OK;
+}
+
+// workspace = [control AWQ_WS_COUNTER_BYTES][exchange region E][scratch region E]; the grouped call has no scratch half
+size_t region_bytes(int64_t M, int64_t N) {
+    const int64_t m = M < 16 ? M : 16;
+    size_t e = (size_t)(64 * m * (N + 512)) * 4;  // up to 64 slabs of [min(M,16), N rounded up to a tile]
+    if (e > ((size_t)32 << 20)) e = (size_t)32 << 20;  // the launchers lower the split to what fits
+    return (e + 255) & ~(size_t)255;
+}
+
+void carve_workspace(AwqGemmArgs* a, void* workspace, size_t bytes, bool scratch) {
+    if (!workspace || bytes <= AWQ_WS_COUNTER_BYTES + (scratch ? 512u : 0u)) return;
+    char* regions = static_cast<char*>(workspace) + AWQ_WS_COUNTER_BYTES;
+    const size_t e = scratch ? ((bytes - AWQ_WS_COUNTER_BYTES) / 2) & ~(size_t)255 : bytes - AWQ_WS_COUNTER_BYTES;
+    a->counters = static_cast<int*>(workspace);
+    a->exchange = reinterpret_cast<float*>(regions);
+    a->exchange_bytes = e;
+    if (!scratch) return;
+    a->partial = reinterpret_cast<float*>(regions + e);
+    a->partial_floats = e / sizeof(float);
+}
+
+// The dispatch of awq_gemm_forward and its fused forms (host only, no launch): the kernel a call asks for FIRST -- the one it names,
+// or AUTO's choice.  fused: gated activations or a _normed / _ex call (the decode kernel alone; the caller has checked that it takes
+// the shape).  AUTO:
+//  - 9 .. 16 rows of a plain call: the register-decoded batched kernel where it is already ahead of the decode kernel -- matrices of
+//    up to 8191 rows and fewer than 64 column tiles (r02: 13.8 vs 15.6 us at 4096 x 11008, M = 16);
+//  - up to 16 rows otherwise: the decode kernel; the naive kernel for the odd shapes it refuses;
+//  - up to 64 rows: the batched kernel where it takes the shape;
+//  - the register-decoded prefill kernel once its 128 x 256 tiles give every CU a block (r02 sweep, profiles/r02_regb_by_m.txt:
+//    4096 x 11008 from M = 768, 11008 x 4096 from M = 2048); below that the LDS-tiled kernel with split-K (smaller tiles, in-launch
+//    combine) fills the chip better; the naive kernel for odd shapes.
+// Two choices can still fall through at run time, on their launcher's answer: see gemm_forward.
+unsigned gemm_plan(unsigned kern, int M, int K, int N, int g, bool fused) {
+    if (kern != AWQ_GEMM_KERNEL_AUTO) return kern;
+    if (!fused && M >= 9 && M <= 16 && K < 8192 && (N + 255) / 256 < 64 && awq_gemm_skinny_supports(M, K, N, g)) return AWQ_GEMM_KERNEL_SKINNY;
+    if (M <= 16) return awq_gemv_mfma_supports(M, K, N, g, 2) ? AWQ_GEMM_KERNEL_MFMA_GEMV : AWQ_GEMM_KERNEL_NAIVE;
+    if (M <= 64 && awq_gemm_skinny_supports(M, K, N, g)) return AWQ_GEMM_KERNEL_SKINNY;
+    if (awq_gemm_regb_supports(M, K, N, g) && (int64_t)((M + 127) / 128) * ((N + 255) / 256) >= 256) return AWQ_GEMM_KERNEL_REGB;
+    return awq_gemm_tiled_supports(M, K, N, g) ? AWQ_GEMM_KERNEL_TILED : AWQ_GEMM_KERNEL_NAIVE;
+}
+
+// awq_gemm_forward, _normed and _ex: the C ABI's arguments travel in the published struct.  extras: a _normed / _ex call -- the
+// decode kernel only, in-launch combine only -- whether or not it carries a norm weight (an _ex call with add_residual or ssq_out
+// alone sets no gated mode and is restricted all the same).
+int gemm_forward(const AwqGemmEx& e, bool extras) {
+    const uint32_t flags = e.flags;
+    const bool empty = e.M == 0 || e.N == 0;
+    AwqGemmArgs a;
+    int rc = check_gemm(&a, e.x, e.qweight, e.scales, e.qzeros, e.y, e.M, e.K, e.N, e.group_size, e.stream, empty);
+    if (rc || empty) return rc;
+    if (e.workspace && !aligned16(e.workspace)) return AWQ_ERR_BAD_ALIGNMENT;
+    a.bias = e.bias;
+    carve_workspace(&a, e.workspace, e.workspace_bytes, true);
+
+    a.x_gated = (flags & AWQ_GEMM_FLAG_X_GATED_SILU) ? 1 : 0;
+    if (e.norm_weight) {
+        if (a.x_gated) return AWQ_ERR_UNSUPPORTED;
+        a.x_gated = 2;
+        a.res_in = e.residual_in; a.res_out = e.residual_out; a.norm_w = e.norm_weight; a.norm_eps = e.norm_eps;
+        a.ssq_in = e.ssq_in; a.ssq_in_tiles = (int)e.ssq_in_tiles;
+    }
+    a.add_res = e.add_residual; a.ssq_out = e.ssq_out;
+    const bool fused = a.x_gated || extras;
+    const unsigned asked = AWQ_GEMM_FLAG_KERNEL(flags);
+    if (fused && (a.M > 16 || !awq_gemv_mfma_supports(a.M, a.K, a.N, a.g, 2))) return AWQ_ERR_UNSUPPORTED;
+    if (extras && (a.M > 4 || (flags & AWQ_GEMM_FLAG_TWO_PASS))) return AWQ_ERR_UNSUPPORTED;
+    if (fused && asked != AWQ_GEMM_KERNEL_AUTO && asked != AWQ_GEMM_KERNEL_MFMA_GEMV) return AWQ_ERR_UNSUPPORTED;
+    if (extras && AWQ_GEMM_FLAG_NLOG(flags) == 4) return AWQ_ERR_UNSUPPORTED;  // the epilogue assumes 256-column tiles
+    int nlog = (int)AWQ_GEMM_FLAG_NLOG(flags);
+    int splitk = (int)AWQ_GEMM_FLAG_SPLITK(flags);
+    if ((int64_t)a.K * a.N / 2 >= ((int64_t)1 << 31)) return AWQ_ERR_UNSUPPORTED;  // 32-bit buffer offsets
+
+    unsigned kern = gemm_plan(asked, a.M, a.K, a.N, a.g, fused);
+    if (asked == AWQ_GEMM_KERNEL_AUTO && kern == AWQ_GEMM_KERNEL_MFMA_GEMV) {  // (the tuning bits are a named kernel's)
+        rc = awq_launch_gemv_mfma(a, 0, 0, 0, 0, false);
+        if (rc != AWQ_ERR_UNSUPPORTED) {
+            g_last_kernel = "gemv_mfma";
+            return rc;
+        }
+        if (fused) return AWQ_ERR_UNSUPPORTED;
+        kern = AWQ_GEMM_KERNEL_NAIVE;  // M <= 16 that the decode launcher refused: odd shapes
+    }
+    switch (kern) {
+        case AWQ_GEMM_KERNEL_NAIVE:
+            g_last_kernel = "naive";
+            return awq_launch_gemm_naive(a);
+        case AWQ_GEMM_KERNEL_VALU: {
+            if (nlog == 0) nlog = 3;
+            if (splitk == 0) splitk = awq_gemv_valu_default_split(a.K, a.N, nlog);
+            while (splitk > 1 && (size_t)splitk * a.M * a.N * 4 > a.partial_floats * sizeof(float)) --splitk;
+            g_last_kernel = "gemv_valu";
+            return awq_launch_gemv_valu(a, nlog, splitk, (flags & AWQ_GEMM_FLAG_NO_NT) == 0);
+        }
+        case AWQ_GEMM_KERNEL_MFMA_GEMV: {
+            if (a.M > 16) return AWQ_ERR_UNSUPPORTED;
+            g_last_kernel = "gemv_mfma";
+            return awq_launch_gemv_mfma(a, nlog, (int)AWQ_GEMM_FLAG_WAVES(flags), (int)AWQ_GEMM_FLAG_UNIT(flags), splitk,
+                                        (flags & AWQ_GEMM_FLAG_TWO_PASS) != 0);
+        }
+        case AWQ_GEMM_KERNEL_TILED:
+            g_last_kernel = "gemm_tiled";
+            return awq_launch_gemm_tiled(a, block_width(flags, true), splitk);
+        case AWQ_GEMM_KERNEL_SKINNY: {
+            rc = awq_launch_gemm_skinny(a, splitk);
+            if (rc != AWQ_ERR_UNSUPPORTED || asked != AWQ_GEMM_KERNEL_AUTO || !awq_gemm_tiled_supports(a.M, a.K, a.N, a.g)) {
+                g_last_kernel = "gemm_skinny";
+                return rc;
+            }
+            g_last_kernel = "gemm_tiled";  // AUTO: a slice that does not fit (very wide matrices at M > 32): the LDS-tiled kernel
+            return awq_launch_gemm_tiled(a, 0, 0);
+        }
+        case AWQ_GEMM_KERNEL_REGB:
+            g_last_kernel = "gemm_regb";
+            return awq_launch_gemm_regb(a, block_width(flags, true));
+        default:
+            return AWQ_ERR_UNSUPPORTED;
+    }
+}
+
+// awq_grouped_gemm_prefill and _ex.  ex: the flag bits and x_div are validated, and the gather / scatter bits read (the plain entry
+// looks at the tile-height field alone: as published)
+int grouped_prefill(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* y,
+                    const int32_t* seg_offsets, const int32_t* row_map, const float* pair_weights, int64_t P, int64_t x_div,
+                    int64_t num_experts, int64_t K, int64_t N, int64_t group_size, uint32_t flags, void* stream, bool ex) {
+    AwqGroupedArgs r;
+    r.seg = seg_offsets; r.row_map = row_map; r.pair_weights = pair_weights;
+    r.gather = ex && (flags & AWQ_GROUPED_PREFILL_GATHER_X); r.scatter = ex && (flags & AWQ_GROUPED_PREFILL_SCATTER_Y);
+    const bool empty = P == 0 || N == 0;
+    AwqGemmArgs a;
+    const int rc = check_gemm(&a, x, qweight, scales, qzeros, y, P, K, N, group_size, stream, empty,
+                              num_experts >= 1 && num_experts <= 4096 &&
+                                  (!ex || (x_div >= 1 && !(flags & ~(0xF0u | AWQ_GROUPED_PREFILL_GATHER_X | AWQ_GROUPED_PREFILL_SCATTER_Y)))),
+                              seg_offsets && (row_map || !(r.gather || r.scatter || pair_weights)));
+    if (rc || empty) return rc;
+    r.num_experts = (int)num_experts; r.x_div = (int)x_div;
+    g_last_kernel = "gemm_regb_grouped";
+    return awq_launch_gemm_regb_grouped(a, r, block_width(flags, false));
 }
 }  // namespace
 
@@ -44,25 +202,15 @@ int awq_unpack_int4(const int32_t* q, uint8_t* out, int64_t rows, int64_t words,
     return awq_launch_unpack(q, out, rows, words, static_cast<hipStream_t>(stream));
 }
 
+// (no activations, and of the alignments only scales' and out's are looked at: the layout rule is all it shares with check_gemm)
 int awq_dequantize_weights(const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, uint16_t* out,
                            int64_t K, int64_t N, int64_t group_size, void* stream) {
-    int rc = check_gemm_layout(K, N, group_size);
-    if (rc) return rc;
+    if (!gemm_layout(K, N, group_size)) return AWQ_ERR_BAD_SHAPE;
     if (K * N == 0) return AWQ_OK;
     if (!qweight || !scales || !qzeros || !out) return AWQ_ERR_NULL;
     if (!aligned16(scales) || !aligned16(out)) return AWQ_ERR_BAD_ALIGNMENT;
     return awq_launch_dequant(qweight, scales, qzeros, out, K, N, group_size, static_cast<hipStream_t>(stream));
 }
-
-namespace {
-// workspace = [control AWQ_WS_COUNTER_BYTES][exchange region E][scratch region E]
-size_t region_bytes(int64_t M, int64_t N) {
-    const int64_t m = M < 16 ? M : 16;
-    size_t e = (size_t)(64 * m * (N + 512)) * 4;  // up to 64 slabs of [min(M,16), N rounded up to a tile]
-    if (e > ((size_t)32 << 20)) e = (size_t)32 << 20;  // the launchers lower the split to what fits
-    return (e + 255) & ~(size_t)255;
-}
-}  // namespace
 
 size_t awq_gemm_workspace_bytes(int64_t M, int64_t K, int64_t N, int64_t group_size) {
     (void)group_size;
@@ -81,29 +229,18 @@ int awq_gemm_workspace_init(void* workspace, size_t workspace_bytes, void* strea
     return AWQ_OK;
 }
 
-namespace {
-struct NormArgs {  // prologue / epilogue extras of awq_gemm_forward_normed / _ex
-    const uint16_t* res_in;
-    uint16_t* res_out;
-    const uint16_t* weight;  // NULL: no norm prologue
-    float eps;
-    const float* ssq_in = nullptr;
-    int ssq_in_tiles = 0;
-    const uint16_t* add_res = nullptr;
-    float* ssq_out = nullptr;
-};
-int gemm_forward_impl(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
-                      const uint16_t* bias, uint16_t* y, int64_t M, int64_t K, int64_t N, int64_t group_size,
-                      void* workspace, size_t workspace_bytes, uint32_t flags, void* stream, const NormArgs* nrm);
-}  // namespace
-
 int awq_gemm_forward(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
                      const uint16_t* bias, uint16_t* y, int64_t M, int64_t K, int64_t N, int64_t group_size,
                      void* workspace, size_t workspace_bytes, uint32_t flags, void* stream) {
-    return gemm_forward_impl(x, qweight, scales, qzeros, bias, y, M, K, N, group_size, workspace, workspace_bytes, flags,
-                             stream, nullptr);
+    AwqGemmEx e{};
+    e.flags = flags;
+    e.x = x; e.qweight = qweight; e.scales = scales; e.qzeros = qzeros; e.bias = bias; e.y = y;
+    e.M = M; e.K = K; e.N = N; e.group_size = group_size;
+    e.workspace = workspace; e.workspace_bytes = workspace_bytes; e.stream = stream;
+    return gemm_forward(e, false);
 }
 
+// its own checks come before the shape rule: as published
 int awq_gemm_forward_normed(const uint16_t* x, const uint16_t* residual_in, uint16_t* residual_out,
                             const uint16_t* norm_weight, float eps, const int32_t* qweight, const uint16_t* scales,
                             const int32_t* qzeros, const uint16_t* bias, uint16_t* y, int64_t M, int64_t K, int64_t N,
@@ -114,18 +251,21 @@ int awq_gemm_forward_normed(const uint16_t* x, const uint16_t* residual_in, uint
     if (!aligned16(norm_weight) || (residual_in && (!aligned16(residual_in) || !aligned16(residual_out))))
         return AWQ_ERR_BAD_ALIGNMENT;
     if (M > 4 || (flags & AWQ_GEMM_FLAG_X_GATED_SILU)) return AWQ_ERR_UNSUPPORTED;
-    const NormArgs nrm{residual_in, residual_out, norm_weight, eps};
-    return gemm_forward_impl(x, qweight, scales, qzeros, bias, y, M, K, N, group_size, workspace, workspace_bytes, flags,
-                             stream, &nrm);
+    AwqGemmEx e{};
+    e.flags = flags;
+    e.x = x; e.qweight = qweight; e.scales = scales; e.qzeros = qzeros; e.bias = bias; e.y = y;
+    e.M = M; e.K = K; e.N = N; e.group_size = group_size;
+    e.workspace = workspace; e.workspace_bytes = workspace_bytes; e.stream = stream;
+    e.norm_weight = norm_weight; e.norm_eps = eps; e.residual_in = residual_in; e.residual_out = residual_out;
+    return gemm_forward(e, true);
 }
 
 int64_t awq_gemm_ex_ssq_tiles(int64_t N) { return N > 0 ? (N + 255) / 256 : 0; }
 
+// (aliasing residuals and a wrong struct_bytes answer AWQ_ERR_BAD_SHAPE here, a NULL struct AWQ_ERR_NULL: as published)
 int awq_gemm_forward_ex(const AwqGemmEx* e) {
     if (!e) return AWQ_ERR_NULL;
     if (e->struct_bytes != sizeof(AwqGemmEx)) return AWQ_ERR_BAD_SHAPE;
-    NormArgs n{e->residual_in, e->residual_out, e->norm_weight, e->norm_eps};
-    n.ssq_in = e->ssq_in; n.ssq_in_tiles = (int)e->ssq_in_tiles; n.add_res = e->add_residual; n.ssq_out = e->ssq_out;
     if ((e->residual_in == nullptr) != (e->residual_out == nullptr)) return AWQ_ERR_NULL;
     if (e->residual_in && (!e->norm_weight || e->residual_in == e->residual_out)) return AWQ_ERR_BAD_SHAPE;
     if (e->ssq_in && (!e->norm_weight || e->residual_in || e->ssq_in_tiles < 1 || e->ssq_in_tiles > 64)) return AWQ_ERR_BAD_SHAPE;
@@ -133,131 +273,13 @@ int awq_gemm_forward_ex(const AwqGemmEx* e) {
     const uint16_t* ptrs[] = {e->norm_weight, e->residual_in, e->residual_out, e->add_residual};
     for (const uint16_t* q : ptrs)
         if (q && !aligned16(q)) return AWQ_ERR_BAD_ALIGNMENT;
-    return gemm_forward_impl(e->x, e->qweight, e->scales, e->qzeros, e->bias, e->y, e->M, e->K, e->N, e->group_size,
-                             e->workspace, e->workspace_bytes, e->flags, e->stream, &n);
+    return gemm_forward(*e, true);
 }
 
-namespace {
-// M > 16.  The register-decoded prefill kernel wins once its 128 x 256 tiles give every CU a block (r02 sweep,
-// profiles/r02_regb_by_m.txt: 4096 x 11008 from M = 768, 11008 x 4096 from M = 2048); below that the LDS-tiled kernel with
-// split-K (smaller tiles, in-launch combine) fills the chip better.
-bool skinny_before_decode(int64_t M, int64_t K, int64_t N) { return M >= 9 && M <= 16 && K < 8192 && (N + 255) / 256 < 64; }
-
-unsigned auto_kernel_large(int M, int K, int N, int g) {
-    if (M <= 64 && awq_gemm_skinny_supports(M, K, N, g)) return AWQ_GEMM_KERNEL_SKINNY;
-    if (awq_gemm_regb_supports(M, K, N, g) && (int64_t)((M + 127) / 128) * ((N + 255) / 256) >= 256) return AWQ_GEMM_KERNEL_REGB;
-    if (awq_gemm_tiled_supports(M, K, N, g)) return AWQ_GEMM_KERNEL_TILED;
-    return AWQ_GEMM_KERNEL_NAIVE;  // odd shapes
-}
-
-int gemm_forward_impl(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
-                      const uint16_t* bias, uint16_t* y, int64_t M, int64_t K, int64_t N, int64_t group_size,
-                      void* workspace, size_t workspace_bytes, uint32_t flags, void* stream, const NormArgs* nrm) {
-    int rc = check_gemm_layout(K, N, group_size);
-    if (rc) return rc;
-    if (M < 0 || M > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
-    if (M == 0 || N == 0) return AWQ_OK;
-    if (!x || !qweight || !scales || !qzeros || !y) return AWQ_ERR_NULL;
-    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales) || !aligned16(qzeros) || !aligned16(y))
-        return AWQ_ERR_BAD_ALIGNMENT;
-    if (workspace && !aligned16(workspace)) return AWQ_ERR_BAD_ALIGNMENT;
-
-    AwqGemmArgs a;
-    a.x = x; a.qweight = qweight; a.scales = scales; a.qzeros = qzeros; a.bias = bias; a.y = y;
-    a.M = (int)M; a.K = (int)K; a.N = (int)N; a.g = (int)group_size;
-    a.stream = static_cast<hipStream_t>(stream);
-    a.counters = nullptr; a.partial = nullptr; a.partial_floats = 0; a.exchange = nullptr; a.exchange_bytes = 0;
-    if (workspace && workspace_bytes > AWQ_WS_COUNTER_BYTES + 512) {
-        const size_t half = ((workspace_bytes - AWQ_WS_COUNTER_BYTES) / 2) & ~(size_t)255;
-        a.counters = static_cast<int*>(workspace);
-        a.exchange = reinterpret_cast<float*>(static_cast<char*>(workspace) + AWQ_WS_COUNTER_BYTES);
-        a.exchange_bytes = half;
-        a.partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + AWQ_WS_COUNTER_BYTES + half);
-        a.partial_floats = half / sizeof(float);
-    }
-
-    a.x_gated = (flags & AWQ_GEMM_FLAG_X_GATED_SILU) ? 1 : 0;
-    if (nrm) {
-        if (nrm->weight) {
-            if (a.x_gated) return AWQ_ERR_UNSUPPORTED;
-            a.x_gated = 2;
-            a.res_in = nrm->res_in; a.res_out = nrm->res_out; a.norm_w = nrm->weight; a.norm_eps = nrm->eps;
-            a.ssq_in = nrm->ssq_in; a.ssq_in_tiles = nrm->ssq_in_tiles;
-        }
-        a.add_res = nrm->add_res; a.ssq_out = nrm->ssq_out;
-    }
-    const bool extras = nrm != nullptr;  // decode kernel only, in-launch combine only
-    if ((a.x_gated || extras) && (M > 16 || !awq_gemv_mfma_supports(a.M, a.K, a.N, a.g, 2))) return AWQ_ERR_UNSUPPORTED;
-    if (extras && (M > 4 || (flags & AWQ_GEMM_FLAG_TWO_PASS))) return AWQ_ERR_UNSUPPORTED;
-    unsigned kern = AWQ_GEMM_FLAG_KERNEL(flags);
-    if ((a.x_gated || extras) && kern != AWQ_GEMM_KERNEL_AUTO && kern != AWQ_GEMM_KERNEL_MFMA_GEMV) return AWQ_ERR_UNSUPPORTED;
-    if (extras && AWQ_GEMM_FLAG_NLOG(flags) == 4) return AWQ_ERR_UNSUPPORTED;  // the epilogue assumes 256-column tiles
-    int nlog = (int)AWQ_GEMM_FLAG_NLOG(flags);
-    int splitk = (int)AWQ_GEMM_FLAG_SPLITK(flags);
-    const int waves = (int)AWQ_GEMM_FLAG_WAVES(flags);
-    const bool two_pass = (flags & AWQ_GEMM_FLAG_TWO_PASS) != 0;
-    const bool nt = (flags & AWQ_GEMM_FLAG_NO_NT) == 0;
-    if ((int64_t)K * N / 2 >= ((int64_t)1 << 31)) return AWQ_ERR_UNSUPPORTED;  // 32-bit buffer offsets
-
-    if (kern == AWQ_GEMM_KERNEL_AUTO) {
-        // 9 .. 16 rows: the register-decoded batched kernel is already ahead of the decode kernel on matrices of up to 8191
-        // rows and fewer than 64 column tiles (plain calls only; r02: 13.8 vs 15.6 us at 4096 x 11008, M = 16)
-        const bool skinny_first = skinny_before_decode(M, K, N) && !a.x_gated && !extras && awq_gemm_skinny_supports(a.M, a.K, a.N, a.g);
-        if (M <= 16 && !skinny_first && awq_gemv_mfma_supports(a.M, a.K, a.N, a.g, 2)) {
-            rc = awq_launch_gemv_mfma(a, 0, 0, 0, 0, false);
-            if (rc != AWQ_ERR_UNSUPPORTED) {
-                g_last_kernel = "gemv_mfma";
-                return rc;
-            }
-        }
-        if (a.x_gated || extras) return AWQ_ERR_UNSUPPORTED;
-        kern = (M > 16 || skinny_first) ? auto_kernel_large(a.M, a.K, a.N, a.g) : AWQ_GEMM_KERNEL_NAIVE;  // M <= 16 that the decode kernel refused: odd shapes
-    }
-    switch (kern) {
-        case AWQ_GEMM_KERNEL_NAIVE:
-            g_last_kernel = "naive";
-            return awq_launch_gemm_naive(a);
-        case AWQ_GEMM_KERNEL_VALU: {
-            if (nlog == 0) nlog = 3;
-            if (splitk == 0) splitk = awq_gemv_valu_default_split(a.K, a.N, nlog);
-            while (splitk > 1 && (size_t)splitk * a.M * a.N * 4 > a.partial_floats * sizeof(float)) --splitk;
-            g_last_kernel = "gemv_valu";
-            return awq_launch_gemv_valu(a, nlog, splitk, nt);
-        }
-        case AWQ_GEMM_KERNEL_MFMA_GEMV: {
-            if (M > 16) return AWQ_ERR_UNSUPPORTED;
-            g_last_kernel = "gemv_mfma";
-            return awq_launch_gemv_mfma(a, nlog, waves, (int)AWQ_GEMM_FLAG_UNIT(flags), splitk, two_pass);
-        }
-        case AWQ_GEMM_KERNEL_TILED: {
-            g_last_kernel = "gemm_tiled";
-            return awq_launch_gemm_tiled(a, nlog == 2 ? 256 : (nlog == 1 ? 128 : 0), splitk);
-        }
-        case AWQ_GEMM_KERNEL_SKINNY: {
-            rc = awq_launch_gemm_skinny(a, splitk);
-            if (rc != AWQ_ERR_UNSUPPORTED || AWQ_GEMM_FLAG_KERNEL(flags) != AWQ_GEMM_KERNEL_AUTO || !awq_gemm_tiled_supports(a.M, a.K, a.N, a.g)) {
-                g_last_kernel = "gemm_skinny";
-                return rc;
-            }
-            g_last_kernel = "gemm_tiled";  // AUTO: a slice that does not fit (very wide matrices at M > 32): the LDS-tiled kernel
-            return awq_launch_gemm_tiled(a, 0, 0);
-        }
-        case AWQ_GEMM_KERNEL_REGB: {
-            g_last_kernel = "gemm_regb";
-            return awq_launch_gemm_regb(a, nlog == 2 ? 256 : (nlog == 1 ? 128 : 0));
-        }
-        default:
-            return AWQ_ERR_UNSUPPORTED;
-    }
-}
-
-}  // namespace
-
+// Which kernel awq_gemm_forward's AUTO dispatch takes first for a plain call (gemm_plan).  -1: an invalid shape.
 int awq_gemm_auto_kernel(int64_t M, int64_t K, int64_t N, int64_t group_size) {
-    if (M <= 0 || K <= 0 || N <= 0 || M > INT32_MAX || check_gemm_layout(K, N, group_size)) return -1;
-    if (skinny_before_decode(M, K, N) && awq_gemm_skinny_supports((int)M, (int)K, (int)N, (int)group_size)) return AWQ_GEMM_KERNEL_SKINNY;
-    if (M <= 16 && awq_gemv_mfma_supports((int)M, (int)K, (int)N, (int)group_size, 2)) return AWQ_GEMM_KERNEL_MFMA_GEMV;
-    return M > 16 ? (int)auto_kernel_large((int)M, (int)K, (int)N, (int)group_size) : (int)AWQ_GEMM_KERNEL_NAIVE;
+    if (M <= 0 || K <= 0 || N <= 0 || M > INT32_MAX || !gemm_layout(K, N, group_size)) return -1;
+    return (int)gemm_plan(AWQ_GEMM_KERNEL_AUTO, (int)M, (int)K, (int)N, (int)group_size, false);
 }
 
 int awq_gemm_workspace_status(const void* workspace, void* stream, int32_t* err_out) {
@@ -324,47 +346,31 @@ int awq_grouped_gemm_forward_ex(const uint16_t* x, const int32_t* qweight, const
                                 int64_t x_div, int64_t block_rows, int64_t max_blocks, int64_t num_experts, int64_t K,
                                 int64_t N, int64_t group_size, void* workspace, size_t workspace_bytes, uint32_t flags,
                                 void* stream) {
-    if (flags & ~AWQ_GEMM_FLAG_X_GATED_SILU) return AWQ_ERR_UNSUPPORTED;
-    int rc = check_gemm_layout(K, N, group_size);
-    if (rc) return rc;
-    if (!(block_rows == 8 || block_rows == 16)) return AWQ_ERR_BAD_SHAPE;
-    if (num_pairs < 0 || x_div < 1 || max_blocks < 0 || num_experts < 1) return AWQ_ERR_BAD_SHAPE;
-    if (num_pairs == 0 || max_blocks == 0 || N == 0) return AWQ_OK;
-    if (!x || !qweight || !scales || !qzeros || !y || !sorted_token_ids || !expert_ids || !num_tokens_post_padded)
-        return AWQ_ERR_NULL;
-    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales) || !aligned16(qzeros) || !aligned16(y))
-        return AWQ_ERR_BAD_ALIGNMENT;
+    if (flags & ~AWQ_GEMM_FLAG_X_GATED_SILU) return AWQ_ERR_UNSUPPORTED;  // before anything else: as published
+    const bool empty = num_pairs == 0 || max_blocks == 0 || N == 0;
+    AwqGemmArgs a;  // M: the rows of a token block
+    const int rc = check_gemm(&a, x, qweight, scales, qzeros, y, block_rows, K, N, group_size, stream, empty,
+                              (block_rows == 8 || block_rows == 16) && num_pairs >= 0 && x_div >= 1 && max_blocks >= 0 && num_experts >= 1,
+                              sorted_token_ids && expert_ids && num_tokens_post_padded);
+    if (rc || empty) return rc;
     if ((int64_t)num_experts * K * N / 2 >= ((int64_t)1 << 40)) return AWQ_ERR_UNSUPPORTED;
     if ((int64_t)K * N / 2 >= ((int64_t)1 << 31)) return AWQ_ERR_UNSUPPORTED;
-    AwqGemmArgs a;
-    a.x = x; a.qweight = qweight; a.scales = scales; a.qzeros = qzeros; a.bias = nullptr; a.y = y;
-    a.M = (int)block_rows; a.K = (int)K; a.N = (int)N; a.g = (int)group_size;
     a.x_gated = (flags & AWQ_GEMM_FLAG_X_GATED_SILU) ? 1 : 0;
-    a.stream = static_cast<hipStream_t>(stream);
-    a.counters = nullptr; a.partial = nullptr; a.partial_floats = 0; a.exchange = nullptr; a.exchange_bytes = 0;
-    if (workspace && workspace_bytes > AWQ_WS_COUNTER_BYTES) {  // [control][exchange]: no scratch half here
-        a.counters = static_cast<int*>(workspace);
-        a.exchange = reinterpret_cast<float*>(static_cast<char*>(workspace) + AWQ_WS_COUNTER_BYTES);
-        a.exchange_bytes = workspace_bytes - AWQ_WS_COUNTER_BYTES;
-    }
+    carve_workspace(&a, workspace, workspace_bytes, false);
     const int64_t NW = N / 8, G = K / group_size;
+    AwqGroupedArgs r;
+    r.sorted_ids = sorted_token_ids; r.expert_ids = expert_ids; r.num_post_pad = num_tokens_post_padded; r.pair_weights = pair_weights;
+    r.num_pairs = (int)num_pairs; r.x_div = (int)x_div; r.max_blocks = (int)max_blocks;
+    r.expert_qw_words = K * NW; r.expert_z_words = G * NW; r.expert_s_halfs = G * N;
     g_last_kernel = "gemv_mfma_grouped";
-    return awq_launch_grouped_gemm(a, sorted_token_ids, expert_ids, num_tokens_post_padded, pair_weights, (int)num_pairs,
-                                   (int)x_div, (int)max_blocks, K * NW, G * NW, G * N);
+    return awq_launch_grouped_gemm(a, r);
 }
 
 int awq_grouped_gemm_prefill(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
                              uint16_t* y, const int32_t* seg_offsets, int64_t P, int64_t num_experts, int64_t K, int64_t N,
                              int64_t group_size, uint32_t flags, void* stream) {
-    int rc = check_gemm_layout(K, N, group_size);
-    if (rc) return rc;
-    if (P < 0 || P > INT32_MAX || num_experts < 1 || num_experts > 4096) return AWQ_ERR_BAD_SHAPE;
-    if (P == 0 || N == 0) return AWQ_OK;
-    if (!x || !qweight || !scales || !qzeros || !y || !seg_offsets) return AWQ_ERR_NULL;
-    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales) || !aligned16(qzeros) || !aligned16(y)) return AWQ_ERR_BAD_ALIGNMENT;
-    g_last_kernel = "gemm_regb_grouped";
-    return awq_launch_gemm_regb_grouped(x, qweight, scales, qzeros, y, seg_offsets, (int)P, (int)num_experts, (int)K, (int)N,
-                                        (int)group_size, AWQ_GEMM_FLAG_NLOG(flags) == 2 ? 256 : 0, static_cast<hipStream_t>(stream));
+    return grouped_prefill(x, qweight, scales, qzeros, y, seg_offsets, nullptr, nullptr, P, 1, num_experts, K, N, group_size, flags,
+                           stream, false);
 }
 
 int awq_moe_sort_pairs(const int32_t* topk_ids, int32_t* order, int32_t* seg_offsets, int64_t num_pairs, int64_t num_experts,
@@ -380,19 +386,8 @@ int awq_grouped_gemm_prefill_ex(const uint16_t* x, const int32_t* qweight, const
                                 uint16_t* y, const int32_t* seg_offsets, const int32_t* row_map, const float* pair_weights,
                                 int64_t P, int64_t x_div, int64_t num_experts, int64_t K, int64_t N, int64_t group_size,
                                 uint32_t flags, void* stream) {
-    int rc = check_gemm_layout(K, N, group_size);
-    if (rc) return rc;
-    if (P < 0 || P > INT32_MAX || num_experts < 1 || num_experts > 4096 || x_div < 1) return AWQ_ERR_BAD_SHAPE;
-    if (flags & ~(0xF0u | AWQ_GROUPED_PREFILL_GATHER_X | AWQ_GROUPED_PREFILL_SCATTER_Y)) return AWQ_ERR_BAD_SHAPE;
-    if (P == 0 || N == 0) return AWQ_OK;
-    if (!x || !qweight || !scales || !qzeros || !y || !seg_offsets) return AWQ_ERR_NULL;
-    const bool gather = flags & AWQ_GROUPED_PREFILL_GATHER_X, scatter = flags & AWQ_GROUPED_PREFILL_SCATTER_Y;
-    if ((gather || scatter || pair_weights) && !row_map) return AWQ_ERR_NULL;
-    if (!aligned16(x) || !aligned16(qweight) || !aligned16(scales) || !aligned16(qzeros) || !aligned16(y)) return AWQ_ERR_BAD_ALIGNMENT;
-    g_last_kernel = "gemm_regb_grouped";
-    return awq_launch_gemm_regb_grouped(x, qweight, scales, qzeros, y, seg_offsets, (int)P, (int)num_experts, (int)K, (int)N,
-                                        (int)group_size, AWQ_GEMM_FLAG_NLOG(flags) == 2 ? 256 : 0, static_cast<hipStream_t>(stream), row_map,
-                                        (int)x_div, pair_weights, gather ? 1 : 0, scatter ? 1 : 0);
+    return grouped_prefill(x, qweight, scales, qzeros, y, seg_offsets, row_map, pair_weights, P, x_div, num_experts, K, N, group_size,
+                           flags, stream, true);
 }
 
 }  // extern "C"
@@ -534,7 +529,7 @@ int awq_gemv_forward(const uint16_t* x, const int32_t* qweight, const uint16_t* 
     switch (plan.kernel) {
         case AWQ_GEMV_KERNEL_PREFILL:
             g_last_kernel = "gemm_regb_nk";
-            return awq_launch_gemm_regb_nk(a, AWQ_GEMM_FLAG_NLOG(flags) == 2 ? 256 : 0);
+            return awq_launch_gemm_regb_nk(a, block_width(flags, false));
         case AWQ_GEMV_KERNEL_BATCH: {
             g_last_kernel = "gemv_batch";
             // the tuning bits are the batch kernel's only when the caller picked it: AUTO plans with 0 (flags written for another kernel
@@ -643,7 +638,7 @@ int awq_gemv_fast_prefill(const uint16_t* x, const int16_t* qweight, const uint1
     if (rc != AWQ_OK) return rc;
     g_last_kernel = "repack_fast+gemm_regb_fz";
     a.qweight = qweight_tmp;  // the GEMM runs on the transposed words
-    return awq_launch_gemm_regb_fz(a, AWQ_GEMM_FLAG_NLOG(flags) == 2 ? 256 : 0);
+    return awq_launch_gemm_regb_fz(a, block_width(flags, false));
 }
 
 size_t awq_gemv_fast_lds_bytes_c(int64_t M, int64_t K, int64_t group_size) {

@@ -685,21 +685,23 @@ int awq_launch_gemm_regb_nk(const AwqGemvArgs& a, int bm) {
 
 // ---- the GROUPED form (MoE prefill, GEMM-layout expert stacks): x / y rows sorted by expert, seg [E + 1] on the device.
 // max_tiles: M tiles the launch provides = ceil(P / bm) + E covers every split of P rows over E experts.
-// row_map / x_div / pair_w / gather / scatter: see RegbParams (all optional; without row_map the rows of x and y are the sorted rows)
-int awq_launch_gemm_regb_grouped(const uint16_t* x, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
-                                 uint16_t* y, const int32_t* seg, int P, int E, int K, int N, int g, int bm, hipStream_t st,
-                                 const int32_t* row_map, int x_div, const float* pair_w, int gather, int scatter) {
+// row_map / x_div / pair_weights / gather / scatter: see RegbParams (all optional; without row_map the rows of x and y are the sorted rows)
+int awq_launch_gemm_regb_grouped(const AwqGemmArgs& a, const AwqGroupedArgs& r, int bm) {
+    const int P = a.M, E = r.num_experts, K = a.K, N = a.N, g = a.g, x_div = r.x_div, gather = r.gather, scatter = r.scatter;
+    const int32_t *seg = r.seg, *row_map = r.row_map;
+    const float* pair_w = r.pair_weights;
+    const hipStream_t st = a.stream;
     if (!awq_gemm_regb_supports(P, K, N, g) || E < 1 || !seg) return AWQ_ERR_UNSUPPORTED;
     if ((gather || scatter || pair_w) && !row_map) return AWQ_ERR_NULL;
     if (bm == 0) bm = 128;
     if (bm != 128 && bm != 256) return AWQ_ERR_UNSUPPORTED;
     RegbParams p;
-    p.qweight = reinterpret_cast<const uint32_t*>(qweight);
-    p.qzeros = reinterpret_cast<const uint32_t*>(qzeros);
-    p.scales = reinterpret_cast<const half_t*>(scales);
-    p.x = reinterpret_cast<const half_t*>(x);
+    p.qweight = reinterpret_cast<const uint32_t*>(a.qweight);
+    p.qzeros = reinterpret_cast<const uint32_t*>(a.qzeros);
+    p.scales = reinterpret_cast<const half_t*>(a.scales);
+    p.x = reinterpret_cast<const half_t*>(a.x);
     p.bias = nullptr;
-    p.y = reinterpret_cast<half_t*>(y);
+    p.y = reinterpret_cast<half_t*>(a.y);
     p.M = P; p.K = K; p.N = N; p.g = g;
     p.KW = p.ZW = p.SW = 0;
     p.seg = seg; p.E = E;

@@ -872,9 +872,8 @@ size_t awq_grouped_workspace_bytes_impl(int max_blocks, int K, int N) {
     return (size_t)AWQ_WS_COUNTER_BYTES + need;
 }
 
-int awq_launch_grouped_gemm(const AwqGemmArgs& a, const int* sorted_ids, const int* expert_ids, const int* num_post_pad,
-                            const float* pair_weights, int num_pairs, int x_div, int max_blocks, int64_t expert_qw_words,
-                            int64_t expert_z_words, int64_t expert_s_halfs) {
+int awq_launch_grouped_gemm(const AwqGemmArgs& a, const AwqGroupedArgs& r) {
+    const int max_blocks = r.max_blocks;
     if (!(a.M == 16 || a.M == 8) || max_blocks < 1 || a.x_gated > 1) return AWQ_ERR_BAD_SHAPE;
     if (max_blocks > 65535) return AWQ_ERR_UNSUPPORTED;  // token blocks ride in gridDim.z; prefill-sized routings take the per-expert path
     if (!awq_gemv_mfma_supports(a.M, a.K, a.N, a.g, 2) || a.g % 32) return AWQ_ERR_UNSUPPORTED;
@@ -935,10 +934,10 @@ int awq_launch_grouped_gemm(const AwqGemmArgs& a, const int* sorted_ids, const i
     p.slabs = a.exchange;
     p.scratch = nullptr;
     p.err = a.counters;
-    p.sorted_ids = sorted_ids; p.expert_ids = expert_ids; p.num_post_pad = num_post_pad;
-    p.pair_weights = pair_weights;
-    p.num_pairs = num_pairs; p.x_div = x_div;
-    p.expert_qw_words = expert_qw_words; p.expert_z_words = expert_z_words; p.expert_s_halfs = expert_s_halfs;
+    p.sorted_ids = r.sorted_ids; p.expert_ids = r.expert_ids; p.num_post_pad = r.num_post_pad;
+    p.pair_weights = r.pair_weights;
+    p.num_pairs = r.num_pairs; p.x_div = r.x_div;
+    p.expert_qw_words = r.expert_qw_words; p.expert_z_words = r.expert_z_words; p.expert_s_halfs = r.expert_s_halfs;
     dim3 grid((unsigned)tiles, (unsigned)c.S, (unsigned)max_blocks);
     if (a.M == 8) {
         if (c.unit == 2) launch_moe<2, true>(p, grid, c.lds, a.stream);

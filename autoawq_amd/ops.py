@@ -187,30 +187,42 @@ def dequantize_weights(qweight, scales, qzeros):
 X_GATED_SILU = 1 << 18  # AWQ_GEMM_FLAG_X_GATED_SILU
 
 
+def _gemm_operands(name, x2d, qweight, scales, qzeros, gated=False):
+    """GEMM layout: the operands of the wrapper `name`, checked (on a HIP device, fp16 activations, matching shapes) and contiguous,
+    a fresh output [M, N] and the sizes the library takes (gated: x2d is [M, 2K] = [gate | up]):
+    (x2d, qweight, scales, qzeros, y, M, K, N, group_size)"""
+    _require_gpu(x2d, qweight, scales, qzeros)
+    if x2d.dtype != torch.float16:
+        raise _lib.AwqHipError(f"{name} expects fp16 activations")
+    x2d, qweight, scales, qzeros = x2d.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
+    M, K = x2d.shape
+    if gated:
+        K //= 2
+    N, G = qweight.shape[1] * 8, qzeros.shape[0]
+    if qweight.shape[0] != K or G == 0 or K % G:
+        raise _lib.AwqHipError(f"{name}: shape mismatch x{tuple(x2d.shape)} qweight{tuple(qweight.shape)} qzeros{tuple(qzeros.shape)}")
+    y = torch.empty((M, N), dtype=torch.float16, device=x2d.device)
+    return x2d, qweight, scales, qzeros, y, M, K, N, K // G
+
+
+def _gemm_workspace(device, M, K, N, group_size, optional=False):
+    """(pointer, bytes) of the current stream's split-K workspace, grown to what this call needs (optional: none where it needs none)"""
+    need = _lib.lib().awq_gemm_workspace_bytes(M, K, N, group_size)
+    ws = workspace(device, need) if need or not optional else None
+    return _ptr(ws), ws.numel() if ws is not None else 0
+
+
 def gemm_forward(x2d, qweight, scales, qzeros, bias=None, flags=0):
     """y [M, N] fp16 = x2d [M, K] fp16 @ dequant(GEMM-layout buffers) (+ bias) (awq_gemm_forward).
     With flags | X_GATED_SILU, x2d is [M, 2K] = [gate | up] and the kernel applies silu(gate) * up
     while staging (M <= 16)."""
-    _require_gpu(x2d, qweight, scales, qzeros, bias)
-    if x2d.dtype != torch.float16:
-        raise _lib.AwqHipError("gemm_forward expects fp16 activations")
-    x2d, qweight, scales, qzeros = x2d.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
-    M, K = x2d.shape
-    if flags & X_GATED_SILU:
-        K //= 2
-    N = qweight.shape[1] * 8
-    G = qzeros.shape[0]
-    if qweight.shape[0] != K or G == 0 or K % G:
-        raise _lib.AwqHipError(f"gemm_forward: shape mismatch x{tuple(x2d.shape)} qweight{tuple(qweight.shape)}")
-    y = torch.empty((M, N), dtype=torch.float16, device=x2d.device)
+    _require_gpu(bias)
+    x2d, qweight, scales, qzeros, y, M, K, N, g = _gemm_operands("gemm_forward", x2d, qweight, scales, qzeros, flags & X_GATED_SILU)
     if M == 0:
         return y
-    L = _lib.lib()
     with torch.cuda.device(x2d.device):
-        need = L.awq_gemm_workspace_bytes(M, K, N, K // G)
-        ws = workspace(x2d.device, need) if need else None
-        rc = L.awq_gemm_forward(_ptr(x2d), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(bias), _ptr(y), M, K, N,
-                                K // G, _ptr(ws), ws.numel() if ws is not None else 0, flags, _stream())
+        rc = _lib.lib().awq_gemm_forward(_ptr(x2d), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(bias), _ptr(y), M, K, N, g,
+                                         *_gemm_workspace(x2d.device, M, K, N, g, optional=True), flags, _stream())
     _lib.check(rc, "awq_gemm_forward")
     return y
 
@@ -219,19 +231,12 @@ def grouped_gemm_prefill(x_sorted, qweight, scales, qzeros, seg_offsets, flags=0
     """MoE prefill (awq_grouped_gemm_prefill): x_sorted [P, K] fp16 = the (token, expert) pairs' rows sorted by expert,
     seg_offsets [E + 1] int32 on the device, qweight [E, K, N/8] / scales [E, K/g, N] / qzeros [E, K/g, N/8] the stacked
     GEMM-layout experts -> y [P, N].  No routing data is read back: capturable."""
-    _require_gpu(x_sorted, qweight, scales, qzeros, seg_offsets)
-    if x_sorted.dtype != torch.float16 or seg_offsets.dtype != torch.int32:
-        raise _lib.AwqHipError("grouped_gemm_prefill expects fp16 activations and int32 offsets")
-    x_sorted, qweight, scales, qzeros = x_sorted.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
-    P, K = x_sorted.shape
-    E, N, G = qweight.shape[0], qweight.shape[2] * 8, qzeros.shape[1]
-    if qweight.shape[1] != K or scales.shape != (E, G, N) or qzeros.shape != (E, G, N // 8) or seg_offsets.numel() != E + 1 or K % G:
-        raise _lib.AwqHipError(f"grouped_gemm_prefill: shape mismatch x{tuple(x_sorted.shape)} qweight{tuple(qweight.shape)} "
-                               f"scales{tuple(scales.shape)} qzeros{tuple(qzeros.shape)} seg{tuple(seg_offsets.shape)}")
+    x_sorted, qweight, scales, qzeros, seg, P, E, K, N, g = _grouped_prefill_operands(
+        "grouped_gemm_prefill", x_sorted, qweight, scales, qzeros, seg_offsets)
     y = torch.empty((P, N), dtype=torch.float16, device=x_sorted.device)
     with torch.cuda.device(x_sorted.device):
-        rc = _lib.lib().awq_grouped_gemm_prefill(_ptr(x_sorted), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(y),
-                                                 _ptr(seg_offsets.contiguous()), P, E, K, N, K // G, flags, _stream())
+        rc = _lib.lib().awq_grouped_gemm_prefill(_ptr(x_sorted), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(y), _ptr(seg),
+                                                 P, E, K, N, g, flags, _stream())
     _lib.check(rc, "awq_grouped_gemm_prefill")
     return y
 
@@ -254,20 +259,29 @@ def moe_sort_pairs(topk_ids, num_experts):
     return order, seg
 
 
+def _grouped_prefill_operands(name, x, qweight, scales, qzeros, seg_offsets, row_map=None):
+    """The grouped prefill GEMM's operands, checked and contiguous, and its sizes (P: the row map's length, else x's rows):
+    (x, qweight, scales, qzeros, seg_offsets, P, E, K, N, group_size)"""
+    _require_gpu(x, qweight, scales, qzeros, seg_offsets, row_map)
+    if x.dtype != torch.float16 or seg_offsets.dtype != torch.int32 or (row_map is not None and row_map.dtype != torch.int32):
+        raise _lib.AwqHipError(f"{name} expects fp16 activations and int32 offsets / row map")
+    x, qweight, scales, qzeros = x.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
+    P, K = x.shape[0] if row_map is None else row_map.numel(), x.shape[1]
+    E, N, G = qweight.shape[0], qweight.shape[2] * 8, qzeros.shape[1]
+    if qweight.shape[1] != K or scales.shape != (E, G, N) or qzeros.shape != (E, G, N // 8) or seg_offsets.numel() != E + 1 or K % G:
+        raise _lib.AwqHipError(f"{name}: shape mismatch x{tuple(x.shape)} qweight{tuple(qweight.shape)} "
+                               f"scales{tuple(scales.shape)} qzeros{tuple(qzeros.shape)} seg{tuple(seg_offsets.shape)}")
+    return x, qweight, scales, qzeros, seg_offsets.contiguous(), P, E, K, N, K // G
+
+
 def grouped_gemm_prefill_ex(x, qweight, scales, qzeros, seg_offsets, row_map, x_div=1, gather=False, scatter=False,
                             pair_weights=None, flags=0, zero_init=False):
     """awq_grouped_gemm_prefill_ex: the grouped prefill GEMM with the sort kept as an index list.  gather: x [T, K] holds the
     tokens, sorted row r reads row row_map[r] / x_div; else x [P, K] is sorted.  scatter: y row row_map[r] (pair order) instead
     of r; pair_weights [P] fp32 by pair index multiply the fp32 product before its one rounding."""
-    _require_gpu(x, qweight, scales, qzeros, seg_offsets, row_map, pair_weights)
-    if x.dtype != torch.float16 or seg_offsets.dtype != torch.int32 or row_map.dtype != torch.int32:
-        raise _lib.AwqHipError("grouped_gemm_prefill_ex expects fp16 activations and int32 offsets / row map")
-    x, qweight, scales, qzeros = x.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
-    P, K = row_map.numel(), x.shape[1]
-    E, N, G = qweight.shape[0], qweight.shape[2] * 8, qzeros.shape[1]
-    if qweight.shape[1] != K or scales.shape != (E, G, N) or qzeros.shape != (E, G, N // 8) or seg_offsets.numel() != E + 1 or K % G:
-        raise _lib.AwqHipError(f"grouped_gemm_prefill_ex: shape mismatch x{tuple(x.shape)} qweight{tuple(qweight.shape)} "
-                               f"scales{tuple(scales.shape)} qzeros{tuple(qzeros.shape)} seg{tuple(seg_offsets.shape)}")
+    _require_gpu(pair_weights)
+    x, qweight, scales, qzeros, seg, P, E, K, N, g = _grouped_prefill_operands(
+        "grouped_gemm_prefill_ex", x, qweight, scales, qzeros, seg_offsets, row_map)
     if (gather and x.shape[0] * x_div < P) or (not gather and x.shape[0] != P):
         raise _lib.AwqHipError(f"grouped_gemm_prefill_ex: x{tuple(x.shape)} does not cover {P} pairs (x_div {x_div})")
     w = pair_weights.contiguous().float().view(-1) if pair_weights is not None else None
@@ -276,9 +290,8 @@ def grouped_gemm_prefill_ex(x, qweight, scales, qzeros, seg_offsets, row_map, x_
     y = (torch.zeros if zero_init else torch.empty)((P, N), dtype=torch.float16, device=x.device)
     f = flags | (GROUPED_PREFILL_GATHER_X if gather else 0) | (GROUPED_PREFILL_SCATTER_Y if scatter else 0)
     with torch.cuda.device(x.device):
-        rc = _lib.lib().awq_grouped_gemm_prefill_ex(_ptr(x), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(y),
-                                                    _ptr(seg_offsets.contiguous()), _ptr(row_map.contiguous()), _ptr(w), P, x_div, E, K, N,
-                                                    K // G, f, _stream())
+        rc = _lib.lib().awq_grouped_gemm_prefill_ex(_ptr(x), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(y), _ptr(seg),
+                                                    _ptr(row_map.contiguous()), _ptr(w), P, x_div, E, K, N, g, f, _stream())
     _lib.check(rc, "awq_grouped_gemm_prefill_ex")
     return y
 
@@ -915,26 +928,19 @@ def kv_dequant_fp8(cache, scales, n, batch=None):
 def gemm_forward_normed(x2d, norm_weight, eps, qweight, scales, qzeros, bias=None, residual=None, flags=0):
     """(y, stream) with y [M, N] = rmsnorm(x2d (+ residual)) * norm_weight @ W and stream = fp16(x2d + residual)
     (None without a residual): awq_gemm_forward_normed, decode batches (M <= 4) of GEMM-layout weights."""
-    _require_gpu(x2d, norm_weight, qweight, scales, qzeros, bias, residual)
-    x2d, qweight, scales, qzeros = x2d.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
-    M, K = x2d.shape
-    N = qweight.shape[1] * 8
-    G = qzeros.shape[0]
-    if x2d.dtype != torch.float16 or qweight.shape[0] != K or G == 0 or K % G or norm_weight.numel() != K:
-        raise _lib.AwqHipError("gemm_forward_normed: fp16 x [M, K], norm weight [K], GEMM-layout buffers expected")
-    y = torch.empty((M, N), dtype=torch.float16, device=x2d.device)
+    _require_gpu(norm_weight, bias, residual)
+    x2d, qweight, scales, qzeros, y, M, K, N, g = _gemm_operands("gemm_forward_normed", x2d, qweight, scales, qzeros)
+    if norm_weight.numel() != K:
+        raise _lib.AwqHipError("gemm_forward_normed: norm weight [K] expected")
     res_out = None
     if residual is not None:
         if residual.shape != x2d.shape or residual.dtype != torch.float16 or not residual.is_contiguous():
             raise _lib.AwqHipError("gemm_forward_normed: residual must be a contiguous fp16 tensor of x's shape")
         res_out = torch.empty_like(residual)
-    L = _lib.lib()
     with torch.cuda.device(x2d.device):
-        need = L.awq_gemm_workspace_bytes(M, K, N, K // G)
-        ws = workspace(x2d.device, need)
-        rc = L.awq_gemm_forward_normed(_ptr(x2d), _ptr(residual), _ptr(res_out), _ptr(norm_weight.contiguous()), float(eps),
-                                       _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(bias), _ptr(y), M, K, N, K // G,
-                                       _ptr(ws), ws.numel(), flags, _stream())
+        rc = _lib.lib().awq_gemm_forward_normed(_ptr(x2d), _ptr(residual), _ptr(res_out), _ptr(norm_weight.contiguous()), float(eps),
+                                                _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(bias), _ptr(y), M, K, N, g,
+                                                *_gemm_workspace(x2d.device, M, K, N, g), flags, _stream())
     _lib.check(rc, "awq_gemm_forward_normed")
     return y, res_out
 
@@ -945,17 +951,9 @@ def gemm_forward_ex(x2d, qweight, scales, qzeros, bias=None, flags=0, norm_weigh
     norm_weight (+ ssq_in [M, tiles] from the producing call, else a statistic pass) normalises x while
     staging; add_residual stores y = fp16(fp16(x W + bias) + add_residual); want_ssq returns the per-tile
     sums of squares of y.  Returns (y, ssq | None)."""
-    _require_gpu(x2d, qweight, scales, qzeros, bias, norm_weight, ssq_in, add_residual)
-    x2d, qweight, scales, qzeros = x2d.contiguous(), qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
-    M, K = x2d.shape
-    if flags & X_GATED_SILU:
-        K //= 2
-    N = qweight.shape[1] * 8
-    G = qzeros.shape[0]
-    if x2d.dtype != torch.float16 or qweight.shape[0] != K or G == 0 or K % G:
-        raise _lib.AwqHipError("gemm_forward_ex: fp16 x [M, K] and GEMM-layout buffers expected")
+    _require_gpu(bias, norm_weight, ssq_in, add_residual)
+    x2d, qweight, scales, qzeros, y, M, K, N, g = _gemm_operands("gemm_forward_ex", x2d, qweight, scales, qzeros, flags & X_GATED_SILU)
     L = _lib.lib()
-    y = torch.empty((M, N), dtype=torch.float16, device=x2d.device)
     ssq = torch.empty((M, L.awq_gemm_ex_ssq_tiles(N)), dtype=torch.float32, device=x2d.device) if want_ssq else None
     if add_residual is not None and (add_residual.shape != y.shape or add_residual.dtype != torch.float16
                                      or not add_residual.is_contiguous()):
@@ -963,14 +961,13 @@ def gemm_forward_ex(x2d, qweight, scales, qzeros, bias=None, flags=0, norm_weigh
     if ssq_in is not None and (ssq_in.dtype != torch.float32 or ssq_in.shape[0] != M or not ssq_in.is_contiguous()):
         raise _lib.AwqHipError("gemm_forward_ex: ssq_in must be a contiguous fp32 [M, tiles] tensor")
     with torch.cuda.device(x2d.device):
-        need = L.awq_gemm_workspace_bytes(M, K, N, K // G)
-        ws = workspace(x2d.device, need)
         e = _lib.AwqGemmEx()
         e.struct_bytes = ctypes.sizeof(_lib.AwqGemmEx)
         e.flags = flags
         e.x, e.qweight, e.scales, e.qzeros, e.bias, e.y = _ptr(x2d), _ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(bias), _ptr(y)
-        e.M, e.K, e.N, e.group_size = M, K, N, K // G
-        e.workspace, e.workspace_bytes, e.stream = _ptr(ws), ws.numel(), _stream()
+        e.M, e.K, e.N, e.group_size = M, K, N, g
+        e.workspace, e.workspace_bytes = _gemm_workspace(x2d.device, M, K, N, g)
+        e.stream = _stream()
         e.norm_weight = _ptr(norm_weight.contiguous()) if norm_weight is not None else None
         e.norm_eps = float(norm_eps)
         e.residual_in = e.residual_out = None
