@@ -13,6 +13,8 @@
 // pins against reference-written checkpoints).  Algorithmic bytes: K N / 2 read + K N / 2 written (+ the small tensors).
 //
 // Tile = 256 output columns (32 words: 128-byte write runs) x 256 k (32 input words: 128-byte read runs) through LDS as [kw][n].
+// awq_repack_gemv_stack_to_gemm: the same tile over a stack of experts, the expert on the grid's y, with the experts to convert
+// picked on the device and an optional row map (below).
 #include "awq_device.h"
 #include "awq_internal.h"
 
@@ -32,18 +34,29 @@ struct RepackParams {
     int main_blocks;  // nt * kt; the blocks after them move the zero points and scales
 };
 
-__global__ __launch_bounds__(512) void awq_repack_nk_kernel(RepackParams p) {
-    __shared__ uint32_t tile[TKW * PITCH];
+// One block's share of one matrix.  MAP: output column c reads input row row_of(c) (the grouped form's de-interleave: the resident
+// w1|w3 stack keeps (gate_j, up_j) as rows 2 j, 2 j + 1; the GEMM-layout columns are gate | up) -- a half wave still reads one
+// row's 128 contiguous bytes, and the stores are the same 128-byte runs.
+template <bool MAP>
+__device__ __forceinline__ int repack_row_of(const RepackParams& p, int c) {
+    if (!MAP) return c;
+    const int h = p.N >> 1;
+    return c < h ? 2 * c : 2 * (c - h) + 1;
+}
+
+template <bool MAP>
+__device__ __forceinline__ void repack_block(const RepackParams& p, uint32_t* tile, int block, int blocks) {
     const int tid = threadIdx.x;
-    if ((int)blockIdx.x < p.main_blocks) {
-        const int tn = blockIdx.x % p.nt, tk = blockIdx.x / p.nt;
+    if (block < p.main_blocks) {
+        const int tn = block % p.nt, tk = block / p.nt;
         const int n0 = tn * TN, kw0 = tk * TKW;
         // ---- in: 256 rows x 32 words, half a wave reads one row's 128 bytes; LDS [kw][n]
 #pragma unroll 4
         for (int i = 0; i < TN * TKW / 512; ++i) {
             const int e = i * 512 + tid, r = e >> 5, kw = e & 31;
             uint32_t v = 0;
-            if (n0 + r < p.N && kw0 + kw < p.KW) v = __builtin_nontemporal_load(p.qw_in + (size_t)(n0 + r) * p.KW + kw0 + kw);
+            if (n0 + r < p.N && kw0 + kw < p.KW)
+                v = __builtin_nontemporal_load(p.qw_in + (size_t)repack_row_of<MAP>(p, n0 + r) * p.KW + kw0 + kw);
             tile[kw * PITCH + r] = v;
         }
         __syncthreads();
@@ -70,13 +83,13 @@ __global__ __launch_bounds__(512) void awq_repack_nk_kernel(RepackParams p) {
     }
     // ---- zero points and scales: item (group, word c): eight rows' zero nibbles of the group -> one word; eight scales
     const int items = p.G * p.NW;
-    for (int e = ((int)blockIdx.x - p.main_blocks) * 512 + tid; e < items; e += ((int)gridDim.x - p.main_blocks) * 512) {
+    for (int e = (block - p.main_blocks) * 512 + tid; e < items; e += (blocks - p.main_blocks) * 512) {
         const int c = e % p.NW, gi = e / p.NW;
         uint32_t o = 0;
         half_t s[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const int n = 8 * c + r;
+            const int n = repack_row_of<MAP>(p, 8 * c + r);
             const uint32_t z = (p.qz_in[(size_t)n * p.ZW + (gi >> 3)] >> (4 * (gi & 7))) & 15u;
             constexpr int POS[8] = {0, 4, 1, 5, 2, 6, 3, 7};  // column r sits in nibble POS[r] (the inverse of ORDER)
             o |= z << (4 * POS[r]);
@@ -85,6 +98,40 @@ __global__ __launch_bounds__(512) void awq_repack_nk_kernel(RepackParams p) {
         p.qz_out[(size_t)gi * p.NW + c] = o;
         *reinterpret_cast<u32x4*>(p.sc_out + (size_t)gi * p.N + 8 * c) = *reinterpret_cast<const u32x4*>(s);
     }
+}
+
+__global__ __launch_bounds__(512) void awq_repack_nk_kernel(RepackParams p) {
+    __shared__ uint32_t tile[TKW * PITCH];
+    repack_block<false>(p, tile, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// ---- a STACK of experts (the single resident copy of a Mixtral layer's experts, modules/fused/moe.py): blockIdx.y = the expert,
+// blockIdx.x = the single-matrix kernel's block.  Which experts are converted is decided HERE, from what the routing left on the
+// device (nothing is read back: capturable): the sorted pairs' row ranges (seg[e + 1] > seg[e]) or the raw top-k ids (expert e
+// occurs among them).  A block of an untouched expert returns before any weight load and writes nothing.
+struct RepackStackParams {
+    RepackParams m;                 // expert 0's pointers
+    size_t qw_in_e, qz_in_e, sc_in_e, qw_out_e, qz_out_e, sc_out_e;  // element strides between experts
+    const int32_t* seg;             // [E + 1] or null
+    const int32_t* ids;             // [num_pairs] or null
+    int num_pairs;
+};
+
+template <bool MAP>
+__global__ __launch_bounds__(512) void awq_repack_stack_kernel(RepackStackParams s) {
+    __shared__ uint32_t tile[TKW * PITCH];
+    const int e = blockIdx.y;
+    if (s.seg) {
+        if (s.seg[e + 1] <= s.seg[e]) return;
+    } else if (s.ids) {
+        int hit = 0;
+        for (int i = threadIdx.x; i < s.num_pairs; i += 512) hit |= s.ids[i] == e;
+        if (!__syncthreads_or(hit)) return;
+    }
+    RepackParams p = s.m;
+    p.qw_in += e * s.qw_in_e; p.qz_in += e * s.qz_in_e; p.sc_in += e * s.sc_in_e;
+    p.qw_out += e * s.qw_out_e; p.qz_out += e * s.qz_out_e; p.sc_out += e * s.sc_out_e;
+    repack_block<MAP>(p, tile, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---- GEMVFast words -> GEMM-layout words (round 6): the prefill route of WQLinear_GEMVFast (awq/modules/linear/gemv_fast.py:203-206
@@ -154,12 +201,20 @@ int awq_repack_gemvfast_to_gemm(const int16_t* qweight, int32_t* qweight_out, in
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
 
-int awq_repack_gemv_to_gemm(const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, int32_t* qweight_out, uint16_t* scales_out,
-                            int32_t* qzeros_out, int64_t K, int64_t N, int64_t group_size, int64_t zeros_width, void* stream) {
+namespace {
+
+// the host checks both GEMV -> GEMM entries share (every refusal before any launch), and the launch geometry of one matrix
+int repack_check(const void* qweight, const void* scales, const void* qzeros, const void* qweight_out, const void* scales_out,
+                 const void* qzeros_out, int64_t K, int64_t N, int64_t group_size, int64_t zeros_width) {
     if (K <= 0 || N <= 0 || group_size <= 0 || K % group_size || K % 8 || N % 8 || zeros_width <= 0) return AWQ_ERR_BAD_SHAPE;
     if (zeros_width * 8 < K / group_size || K > INT32_MAX || N > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
     if (!qweight || !scales || !qzeros || !qweight_out || !scales_out || !qzeros_out) return AWQ_ERR_NULL;
     if (((uintptr_t)scales_out & 15) || ((uintptr_t)qweight & 3)) return AWQ_ERR_BAD_ALIGNMENT;
+    return AWQ_OK;
+}
+
+RepackParams repack_fill(const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, int32_t* qweight_out, uint16_t* scales_out,
+                         int32_t* qzeros_out, int64_t K, int64_t N, int64_t group_size, int64_t zeros_width, int* small_blocks) {
     RepackParams p;
     p.qw_in = reinterpret_cast<const uint32_t*>(qweight);
     p.qz_in = reinterpret_cast<const uint32_t*>(qzeros);
@@ -173,8 +228,41 @@ int awq_repack_gemv_to_gemm(const int32_t* qweight, const uint16_t* scales, cons
     p.kt = (p.KW + TKW - 1) / TKW;
     p.main_blocks = p.nt * p.kt;
     const int small_items = p.G * p.NW;
-    int small_blocks = (small_items + 511) / 512;
-    if (small_blocks > 256) small_blocks = 256;
+    *small_blocks = (small_items + 511) / 512;
+    if (*small_blocks > 256) *small_blocks = 256;
+    return p;
+}
+
+}  // namespace
+
+int awq_repack_gemv_to_gemm(const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, int32_t* qweight_out, uint16_t* scales_out,
+                            int32_t* qzeros_out, int64_t K, int64_t N, int64_t group_size, int64_t zeros_width, void* stream) {
+    if (const int rc = repack_check(qweight, scales, qzeros, qweight_out, scales_out, qzeros_out, K, N, group_size, zeros_width)) return rc;
+    int small_blocks;
+    const RepackParams p = repack_fill(qweight, scales, qzeros, qweight_out, scales_out, qzeros_out, K, N, group_size, zeros_width, &small_blocks);
     hipLaunchKernelGGL(awq_repack_nk_kernel, dim3((unsigned)(p.main_blocks + small_blocks)), dim3(512), 0, static_cast<hipStream_t>(stream), p);
+    return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
+}
+
+int awq_repack_gemv_stack_to_gemm(const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, int32_t* qweight_out,
+                                  uint16_t* scales_out, int32_t* qzeros_out, const int32_t* seg_offsets, const int32_t* topk_ids,
+                                  int64_t num_pairs, int64_t num_experts, int64_t K, int64_t N, int64_t group_size, int64_t zeros_width,
+                                  uint32_t flags, void* stream) {
+    if (flags & ~AWQ_REPACK_DEINTERLEAVE_HALVES) return AWQ_ERR_BAD_SHAPE;
+    if (num_experts < 0 || num_experts > 65535 || num_pairs < 0 || num_pairs > INT32_MAX) return AWQ_ERR_BAD_SHAPE;
+    if (seg_offsets && topk_ids) return AWQ_ERR_BAD_SHAPE;  // one selector at most
+    if (const int rc = repack_check(qweight, scales, qzeros, qweight_out, scales_out, qzeros_out, K, N, group_size, zeros_width)) return rc;
+    if (num_experts == 0 || (topk_ids && num_pairs == 0)) return AWQ_OK;  // no expert to convert
+    RepackStackParams s;
+    int small_blocks;
+    s.m = repack_fill(qweight, scales, qzeros, qweight_out, scales_out, qzeros_out, K, N, group_size, zeros_width, &small_blocks);
+    s.qw_in_e = (size_t)N * s.m.KW; s.qz_in_e = (size_t)N * s.m.ZW; s.sc_in_e = (size_t)N * s.m.SW;
+    s.qw_out_e = (size_t)K * s.m.NW; s.qz_out_e = (size_t)s.m.G * s.m.NW; s.sc_out_e = (size_t)s.m.G * N;
+    s.seg = seg_offsets; s.ids = topk_ids; s.num_pairs = (int)num_pairs;
+    const dim3 grid((unsigned)(s.m.main_blocks + small_blocks), (unsigned)num_experts);
+    if (flags & AWQ_REPACK_DEINTERLEAVE_HALVES)
+        hipLaunchKernelGGL(awq_repack_stack_kernel<true>, grid, dim3(512), 0, static_cast<hipStream_t>(stream), s);
+    else
+        hipLaunchKernelGGL(awq_repack_stack_kernel<false>, grid, dim3(512), 0, static_cast<hipStream_t>(stream), s);
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }

@@ -112,7 +112,7 @@ def fuse_llama(hf_model, max_seq_len=2048, decode_layout="auto", kv_cache_dtype=
     return FusedCausalLM(fused, hf_model.lm_head, checkpoint_layout=src, decode_layout=target or src, kv_cache_dtype=kv_cache_dtype)
 
 
-def fuse_mixtral(hf_model, max_seq_len=2048, decode_layout="auto", kv_cache_dtype="fp16"):
+def fuse_mixtral(hf_model, max_seq_len=2048, decode_layout="auto", kv_cache_dtype="fp16", expert_copies=2):
     """`MixtralFuser.fuse_transformer` (awq/models/mixtral.py:97-187) for a Mixtral-style model in the per-expert form AWQ
     checkpoints are written in (`model.layers[i].block_sparse_moe.{gate, top_k, experts[e].{w1, w2, w3}}`): per layer fuse
     q|k|v, wrap the norms, and -- when the experts are WQLinear_GEMM -- concatenate each expert's w1|w3 on N, stack the experts
@@ -122,8 +122,20 @@ def fuse_mixtral(hf_model, max_seq_len=2048, decode_layout="auto", kv_cache_dtyp
     with a decode layout they also get GEMV-layout TWINS (`moe.build_decode_twins`: a second resident copy of the experts, w1|w3
     with its gate / up rows interleaved), which decode-sized steps run through the row-streaming kernel -- Mixtral shape, bs = 4:
     114 us per block against 132 us on the GEMM-layout stacks.  decode_layout=None: no repack, no twins.
-    kv_cache_dtype as in `fuse_llama`."""
+    kv_cache_dtype as in `fuse_llama`.
+    expert_copies: 2 (default) keeps both the GEMM-layout stacks and the twins resident -- for Mixtral-8x7B about 48 GB of experts.
+    1 (opt-in, needs a decode layout) keeps ONLY the GEMV-layout stacks, as registered buffers (`moe.build_single_copy`,
+    `utils.convert.ExpertStackResident`): decode steps of up to `moe.ROWS_MAX_PAIRS_SINGLE` pairs run exactly as on the twins;
+    larger token counts first repack the experts they touch into one GEMM-layout workspace per device (`ops.expert_workspace`,
+    about 0.49 GB for Mixtral-8x7B) and then run the same grouped kernels -- the same bits, and the repack's time on top
+    (profiles/moe_single_copy.txt).  ValueError where the experts are not GEMM-layout modules or the row-streaming kernel does
+    not take their shape: never a silent fallback to two copies."""
     _check_kv_cache_dtype("fuse_mixtral", kv_cache_dtype)
+    if expert_copies not in (1, 2):
+        raise ValueError(f"fuse_mixtral: expert_copies must be 1 or 2, got {expert_copies!r}")
+    if expert_copies == 1 and decode_layout is None:
+        raise ValueError("fuse_mixtral: expert_copies=1 keeps the experts in the decode layout alone and needs one: "
+                         "decode_layout='auto' or 'gemv'")
     cfg = hf_model.config
     src = _layout_of(hf_model.model)
     target = src
@@ -149,11 +161,20 @@ def fuse_mixtral(hf_model, max_seq_len=2048, decode_layout="auto", kv_cache_dtyp
             w1w3 = [fuse_linears([e.w1, e.w3], dev) for e in moe.experts]
             moe = FusedSparseMoeBlock(top_k=moe.top_k, gate=moe.gate, ws=fuse_linears(w1w3, dev, dim=0, operation=torch.stack),
                                       w2s=fuse_linears([e.w2 for e in moe.experts], dev, dim=0, operation=torch.stack))
-            if decode_layout is not None and moe.ws.qweight.is_cuda:
+            if expert_copies == 1:
+                from .modules.fused.moe import build_single_copy
+
+                ws, w2s = build_single_copy(moe.ws, moe.w2s)
+                moe = FusedSparseMoeBlock(top_k=moe.top_k, gate=moe.gate, ws=ws, w2s=w2s)  # the GEMM-layout stacks are dropped here
+                target = "gemv (attention projections, experts: single copy)"
+            elif decode_layout is not None and moe.ws.qweight.is_cuda:
                 from .modules.fused.moe import build_decode_twins
 
                 build_decode_twins(moe.ws, moe.w2s)
                 target = "gemv (attention projections, expert twins for decode) + gemm (experts)"
+        elif expert_copies == 1:
+            raise ValueError("fuse_mixtral: expert_copies=1 needs the experts as WQLinear_GEMM modules, got "
+                             f"{type(moe.experts[0].w1).__name__}")
         rope_theta = getattr(cfg, "rope_theta", None)
         if rope_theta is None:
             rope_theta = (getattr(cfg, "rope_parameters", None) or {}).get("rope_theta", 10000.0)

@@ -145,6 +145,7 @@ def release_workspaces():
     _workspaces.clear()
     _moe_workspaces.clear()
     _attn_workspaces.clear()
+    _expert_workspaces.clear()
     del _retired[:]
     del _retired_raw[:]
 
@@ -416,6 +417,73 @@ def repack_gemv_to_gemm(qweight, scales, qzeros, group_size):
     with torch.cuda.device(qweight.device):
         _lib.check(_lib.lib().awq_repack_gemv_to_gemm(_ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(qw), _ptr(sc), _ptr(qz), K, N,
                                                       group_size, qzeros.shape[1], _stream()), "awq_repack_gemv_to_gemm")
+    return qw, sc, qz
+
+
+REPACK_DEINTERLEAVE_HALVES = 1  # include/awq_hip.h AWQ_REPACK_DEINTERLEAVE_HALVES
+
+_expert_workspaces = {}  # device index -> uint8 buffer: the GEMM-layout temporary of single-copy expert stacks
+
+
+def expert_workspace(device, E, K, N, G):
+    """(qweight [E, K, N/8] i32, scales [E, G, N] f16, qzeros [E, G, N/8] i32): views of ONE persistent buffer per device, grown to
+    the largest expert stack seen there and shared by every layer and both projections of every single-copy MoE block
+    (modules/fused/moe.py) -- work on one stream runs in order, so the next repack only overwrites weights the GEMM before it has
+    read.  Never (re)allocated while a hipGraph is being captured: a captured step has to find it in place (GraphedDecoder's
+    warm-up step allocates it).  An outgrown buffer is retired, not freed: a graph captured earlier may still replay into it."""
+    nq, ns, nz = E * K * (N // 8) * 4, E * G * N * 2, E * G * (N // 8) * 4
+    oq, os_ = (nq + 255) & ~255, (ns + 255) & ~255
+    need = oq + os_ + nz
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    buf = _expert_workspaces.get(key)
+    if buf is None or buf.numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.AwqHipError(f"expert_workspace: {need} bytes needed on device {key} while a hipGraph is being captured; run "
+                                   "the step once outside the capture first (GraphedDecoder's warm-up does)")
+        if buf is not None:
+            _retired_raw.append(buf)
+        with torch.inference_mode(False):
+            buf = torch.empty(need, dtype=torch.uint8, device=device)
+        _expert_workspaces[key] = buf
+    return (buf[:nq].view(torch.int32).view(E, K, N // 8), buf[oq:oq + ns].view(torch.float16).view(E, G, N),
+            buf[oq + os_:oq + os_ + nz].view(torch.int32).view(E, G, N // 8))
+
+
+def repack_gemv_stack_to_gemm(qweight, scales, qzeros, group_size, out=None, seg_offsets=None, topk_ids=None,
+                              deinterleave_halves=False):
+    """A GEMV-layout expert stack (qweight [E, N, K/8], qzeros [E, N, ZW], scales [E, N, 8 ZW]: utils/convert.py::gemm_stack_to_gemv)
+    -> (qweight [E, K, N/8], scales [E, K/g, N], qzeros [E, K/g, N/8]) in the GEMM layout, bit for bit
+    (awq_repack_gemv_stack_to_gemm, csrc/repack.hip).  out: the three caller-owned buffers (default: the device's
+    expert_workspace).  Only the experts with rows in seg_offsets [E + 1] (moe_sort_pairs) / occurring in topk_ids are converted,
+    picked on the device; the others' parts of `out` are not written.  deinterleave_halves: the inverse of
+    gemm_stack_to_gemv(interleave_halves=True)."""
+    _require_gpu(qweight, scales, qzeros, seg_offsets, topk_ids)
+    qweight, scales, qzeros = qweight.contiguous(), scales.contiguous(), qzeros.contiguous()
+    E, N, KW = qweight.shape
+    K, ZW = KW * 8, qzeros.shape[2]
+    if group_size <= 0 or K % group_size or qzeros.shape[:2] != (E, N) or scales.shape != (E, N, ZW * 8):
+        raise _lib.AwqHipError(f"repack_gemv_stack_to_gemm: shape mismatch qweight{tuple(qweight.shape)} qzeros{tuple(qzeros.shape)} "
+                               f"scales{tuple(scales.shape)} group_size {group_size}")
+    G = K // group_size
+    qw, sc, qz = out if out is not None else expert_workspace(qweight.device, E, K, N, G)
+    if (qw.shape != (E, K, N // 8) or sc.shape != (E, G, N) or qz.shape != (E, G, N // 8) or qw.dtype != torch.int32
+            or sc.dtype != torch.float16 or qz.dtype != torch.int32 or not (qw.is_contiguous() and sc.is_contiguous() and qz.is_contiguous())
+            or qw.device != qweight.device or sc.device != qweight.device or qz.device != qweight.device):
+        raise _lib.AwqHipError("repack_gemv_stack_to_gemm: out must be contiguous (int32 [E, K, N/8], fp16 [E, K/g, N], int32 [E, K/g, N/8]) "
+                               "on the stack's device")
+    pairs = 0
+    for name, t, n in (("seg_offsets", seg_offsets, E + 1), ("topk_ids", topk_ids, None)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or (n is not None and t.numel() != n)):
+            raise _lib.AwqHipError(f"repack_gemv_stack_to_gemm: {name} must be a contiguous int32 tensor" + (f" of {n}" if n else ""))
+    if topk_ids is not None:
+        pairs = topk_ids.numel()
+        if pairs == 0:  # no pair, no expert (an empty tensor has no pointer to tell the library so)
+            return qw, sc, qz
+    with torch.cuda.device(qweight.device):
+        rc = _lib.lib().awq_repack_gemv_stack_to_gemm(_ptr(qweight), _ptr(scales), _ptr(qzeros), _ptr(qw), _ptr(sc), _ptr(qz),
+                                                      _ptr(seg_offsets), _ptr(topk_ids), pairs, E, K, N, group_size, ZW,
+                                                      REPACK_DEINTERLEAVE_HALVES if deinterleave_halves else 0, _stream())
+    _lib.check(rc, "awq_repack_gemv_stack_to_gemm")
     return qw, sc, qz
 
 

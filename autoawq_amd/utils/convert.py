@@ -98,6 +98,38 @@ class ExpertStackGemv:
         self.qweight, self.qzeros, self.scales, self.group_size, self.pairs = qweight, qzeros, scales, group_size, pairs
 
 
+class ExpertStackResident(torch.nn.Module):
+    """The ONLY resident copy of a stacked expert tensor set (`fuse_mixtral(expert_copies=1)`): the GEMV-layout stack of an
+    ExpertStackGemv as registered buffers, so `.to()` / `.cuda()` move it with the model.  `interleaved`: the rows are (gate_j,
+    up_j) pairs of a w1|w3 concatenation (gemm_stack_to_gemv(interleave_halves=True)).  Decode-sized steps read it as it is
+    (the row-streaming kernel); larger token counts repack the experts they touch into a GEMM-layout workspace
+    (ops.repack_gemv_stack_to_gemm, modules/fused/moe.py)."""
+    layout = "gemv"
+
+    def __init__(self, stack):
+        super().__init__()
+        self.register_buffer("qweight", stack.qweight)
+        self.register_buffer("qzeros", stack.qzeros)
+        self.register_buffer("scales", stack.scales)
+        self.group_size = stack.group_size
+        self.interleaved = bool(stack.pairs)
+
+    @property
+    def in_features(self):
+        return self.qweight.shape[2] * 8
+
+    @property
+    def out_features(self):
+        return self.qweight.shape[1]
+
+    def expert_bytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.qweight, self.qzeros, self.scales))
+
+    def extra_repr(self):
+        return (f"experts={self.qweight.shape[0]}, in_features={self.in_features}, out_features={self.out_features}, "
+                f"group_size={self.group_size}, interleaved={self.interleaved}, layout=gemv (single resident copy)")
+
+
 def gemm_stack_to_gemv(qweight, qzeros, scales, interleave_halves=False):
     """Stacked GEMM-layout experts (qweight [E, K, N/8], qzeros [E, K/g, N/8], scales [E, K/g, N]) -> the same integers, zero
     points and scales in the GEMV layout, stacked (qweight [E, N, K/8], qzeros [E, N, ZW], scales [E, N, 8 ZW]); no

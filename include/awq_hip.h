@@ -254,6 +254,22 @@ AWQ_EXPORT int awq_dequantize_weights_gemv(const int32_t* qweight, const uint16_
 AWQ_EXPORT int awq_repack_gemv_to_gemm(const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, int32_t* qweight_out,
                                        uint16_t* scales_out, int32_t* qzeros_out, int64_t K, int64_t N, int64_t group_size,
                                        int64_t zeros_width, void* stream);
+/* The same moves over a STACK of experts (a Mixtral layer's single resident copy, modules/fused/moe.py): qweight [E, N, K/8],
+ * qzeros [E, N, ZW], scales [E, N, 8 ZW] -> qweight_out [E, K, N/8], scales_out [E, K/g, N], qzeros_out [E, K/g, N/8], what
+ * awq_grouped_gemm_prefill[_ex] and awq_grouped_gemm_forward[_ex] read.  One launch; which experts are converted is decided ON THE
+ * DEVICE (nothing is read back: capturable): seg_offsets [E + 1] int32 as awq_moe_sort_pairs writes it -> expert e iff
+ * seg[e + 1] > seg[e]; topk_ids [num_pairs] int32 -> expert e iff it occurs among them; neither -> every expert; both ->
+ * AWQ_ERR_BAD_SHAPE.  The blocks of an expert that is not converted return before any weight load and write NOTHING to its part
+ * of the outputs.  AWQ_REPACK_DEINTERLEAVE_HALVES: input row 2 j -> output column j, row 2 j + 1 -> column N/2 + j (the inverse of
+ * the (gate, up) row pairs the row-streaming kernel's silu-pairs epilogue reads: the outputs are the w1|w3 concatenation of
+ * awq/models/mixtral.py:131-142).  Limits and return codes as awq_repack_gemv_to_gemm; E <= 65535; E == 0, or topk_ids with
+ * num_pairs == 0, is AWQ_OK without a launch. */
+#define AWQ_REPACK_DEINTERLEAVE_HALVES 1u
+AWQ_EXPORT int awq_repack_gemv_stack_to_gemm(const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
+                                             int32_t* qweight_out, uint16_t* scales_out, int32_t* qzeros_out,
+                                             const int32_t* seg_offsets, const int32_t* topk_ids, int64_t num_pairs,
+                                             int64_t num_experts, int64_t K, int64_t N, int64_t group_size, int64_t zeros_width,
+                                             uint32_t flags, void* stream);
 
 /* ---- GEMVFast layout: qweight [N/4, K] i16 (4-row interleave, awq/modules/linear/gemv_fast.py:26-65),
  *      scales [8*ZW, N] f16, qzeros [8*ZW, N] f16 = -(scale*zero) (gemv_fast.py:86-118,175-181) ------- */

@@ -2,7 +2,9 @@
 """BASELINE configs[4]: Mixtral-8x7B-shape AWQ int4 g128 fused MoE MLP, bs=4 decode on 1 MI355X.
 E=8, top-2, hidden 4096, inter 14336: w1|w3 stacked [8, 4096, 3584] i32, w2 [8, 14336, 512] i32.
 Reports us per MoE block (router excluded), bytes of the experts actually hit, GB/s -- after checking the block's
-output against the same experts run one (token, expert) pair at a time through the plain decode kernel."""
+output against the same experts run one (token, expert) pair at a time through the plain decode kernel.
+--expert-copies 1 [--sweep | --prefill | --tokens T ...]: fuse_mixtral's two resident copies of the experts against the opt-in single
+copy, side by side on the same weights (run_copies: times, resident bytes, the stack repack's GB/s)."""
 import os
 import sys
 
@@ -234,6 +236,134 @@ def run_ep(world, dev=None, layers=2, reps=20, verbose=True):
     return {"world": world, "per_rank": per_rank, "busiest_rank_us": worst, "sum_vs_unsharded_max_rel": rel}
 
 
+def _graph_us(step, blocks, dev, reps):
+    """us per MoE block of `step` (which runs `blocks` of them), hipGraph-captured after two eager runs, `reps` replays timed"""
+    s = torch.cuda.Stream(device=dev)
+    with torch.cuda.stream(s):
+        step()
+        step()
+        s.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=s):
+            step()
+        gr.replay()
+        s.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        for _ in range(reps):
+            gr.replay()
+        e1.record(s)
+        e1.synchronize()
+    del gr
+    return e0.elapsed_time(e1) * 1e3 / (reps * blocks)
+
+
+def run_copies(tokens, dev=None, layers=2, reps=20, repeats=3, sweep=False):
+    """fuse_mixtral(expert_copies=2) against expert_copies=1 on the Mixtral-8x7B-shape block, the SAME weights in both modes:
+    us per block at each token count of `tokens` (hipGraph-captured, modes alternating, `repeats` times: the spread is printed),
+    the resident expert bytes of both modes, and the stack repack alone (every expert converted) with its achieved GB/s.
+    sweep: in single-copy mode both the row-streaming kernel and repack + grouped kernel are timed at every count (the
+    hand-over moe.ROWS_MAX_PAIRS_SINGLE is read from that), two-copy mode runs as dispatched."""
+    from autoawq_amd import ops
+    from autoawq_amd.modules.fused import moe
+
+    dev = dev or torch.device("cuda")
+    gen = torch.Generator(device=dev).manual_seed(0)
+    lim = 0x7FFFFFFF
+
+    def experts(K, N):
+        s = Stack()
+        s.qweight = torch.randint(-lim - 1, lim, (E, K, N // 8), dtype=torch.int32, device=dev, generator=gen)
+        s.qzeros = torch.randint(-lim - 1, lim, (E, K // g, N // 8), dtype=torch.int32, device=dev, generator=gen)
+        s.scales = (torch.rand((E, K // g, N), device=dev, generator=gen) * 0.02 + 0.005).half()
+        return s
+
+    two = [(experts(H, 2 * I), experts(I, H)) for _ in range(layers)]  # layers x 733 MB per copy: defeats the 256 MiB L3
+    for a, b in two:
+        moe.build_decode_twins(a, b)
+    # the single copy = the twins' tensors in registered buffers (moe.build_single_copy builds exactly these; shared here to halve the set-up)
+    from autoawq_amd.utils.convert import ExpertStackResident
+
+    one = [(ExpertStackResident(a.decode_twin), ExpertStackResident(b.decode_twin)) for a, b in two]
+    nbytes = lambda t: sum(v.numel() * v.element_size() for v in (t.qweight, t.qzeros, t.scales))
+    by2 = sum(nbytes(t) + nbytes(t.decode_twin) for t in two[0])
+    by1 = sum(t.expert_bytes() for t in one[0])
+    print(f"resident expert bytes per block: expert_copies=2 {by2 / 1e6:.1f} MB (GEMM-layout stacks {sum(nbytes(t) for t in two[0]) / 1e6:.1f} "
+          f"+ twins), expert_copies=1 {by1 / 1e6:.1f} MB; x 32 layers: {32 * by2 / 1e9:.2f} GB / {32 * by1 / 1e9:.2f} GB", flush=True)
+
+    # ---- the repack alone, every expert converted (read + written bytes over device-event time, alternating layers)
+    def spread(v):
+        return f"{min(v):.1f} .. {max(v):.1f}"
+
+    for name, idx in (("w1|w3", 0), ("w2", 1)):
+        r = one[0][idx]
+        out = ops.repack_gemv_stack_to_gemm(r.qweight, r.scales, r.qzeros, g, deinterleave_halves=r.interleaved)
+        src = two[0][idx]
+        assert torch.equal(out[0], src.qweight) and torch.equal(out[2], src.qzeros) and torch.equal(out[1], src.scales), name
+        moved = nbytes(r) + sum(v.numel() * v.element_size() for v in out)
+        us = [_graph_us(lambda: [ops.repack_gemv_stack_to_gemm(p[idx].qweight, p[idx].scales, p[idx].qzeros, g,
+                                                                  deinterleave_halves=p[idx].interleaved) for p in one], layers, dev, reps)
+              for _ in range(repeats)]
+        best = min(us)
+        print(f"repack {name} stack, all {E} experts: {spread(us)} us ({moved / 1e6:.0f} MB read + written -> {moved / best / 1e3:.0f} GB/s; "
+              f"the device's measured copy rate is 6290 GB/s)", flush=True)
+    ws = ops._expert_workspaces[dev.index if dev.index is not None else torch.cuda.current_device()]
+    print(f"GEMM-layout workspace on the device: {ws.numel() / 1e6:.1f} MB", flush=True)
+
+    saved = moe.ROWS_MAX_PAIRS_SINGLE
+    try:
+        for T_ in tokens:
+            x = torch.randn((T_, H), device=dev, generator=gen).half()
+            logits = torch.randn((T_, E), device=dev, generator=gen)
+            hit = len(set(ops.fused_topk(logits, topk, True)[1].reshape(-1).tolist()))
+            use = layers if T_ * topk < moe.PREFILL_MIN_PAIRS else 1
+            r_ = reps if T_ * topk < moe.PREFILL_MIN_PAIRS else max(3, reps // 4)
+            modes = [("expert_copies=2", two, None)]
+            if sweep:
+                modes += [("expert_copies=1 rows", one, 1 << 30), ("expert_copies=1 repack+grouped", one, 0)]
+            else:
+                modes += [("expert_copies=1", one, saved)]
+            res = {m[0]: [] for m in modes}
+            kern, outs = {}, {}
+            for _ in range(repeats):
+                for name, stacks, hand_over in modes:
+                    if hand_over is not None:
+                        if name.endswith("rows") and T_ * topk >= moe.PREFILL_MIN_PAIRS:
+                            continue
+                        moe.ROWS_MAX_PAIRS_SINGLE = hand_over
+                    outs[name] = moe.apply_moe_weights(stacks[0][0], stacks[0][1], x, logits, topk, True)
+                    kern[name] = ops.last_kernel()
+                    res[name].append(_graph_us(lambda: [moe.apply_moe_weights(a, b, x, logits, topk, True) for a, b in stacks[:use]],
+                                               use, dev, r_))
+            for name in res:
+                if not res[name]:
+                    continue
+                same = "" if name == modes[0][0] else (" bit-identical to expert_copies=2" if torch.equal(outs[name], outs[modes[0][0]])
+                                                       else f" max |diff| vs expert_copies=2 {float((outs[name].float() - outs[modes[0][0]].float()).abs().max()):.2e}"
+                                                            if kern[name] != kern[modes[0][0]] else " DIFFERS from expert_copies=2 on the same kernel")
+                print(f"T={T_:4d} ({T_ * topk:4d} pairs, {hit} experts hit) {name:32s} [{kern[name]:18s}] {spread(res[name])} us per block"
+                      f" (median {sorted(res[name])[len(res[name]) // 2]:.1f}){same}", flush=True)
+    finally:
+        moe.ROWS_MAX_PAIRS_SINGLE = saved
+
+
+if __name__ == "__main__" and any(a_.startswith("--expert-copies") for a_ in sys.argv):
+    # --expert-copies N [--sweep] [--prefill]: both modes side by side (N names the mode under study; 2 alone = the plain run)
+    import argparse
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--expert-copies", type=int, choices=(1, 2), default=2)
+    ap.add_argument("--sweep", action="store_true", help="the pair counts of the plain --sweep, rows and repack + grouped kernel")
+    ap.add_argument("--prefill", action="store_true", help="T = 512")
+    ap.add_argument("--tokens", type=int, nargs="*", default=None)
+    ap.add_argument("--repeats", type=int, default=3)
+    a = ap.parse_args()
+    if a.expert_copies == 2 and not (a.sweep or a.prefill or a.tokens):
+        run()
+    else:
+        toks = a.tokens or (((1, 2, 4, 8, 12, 16, 24, 32) if a.sweep else ()) + ((512,) if a.prefill else ())) or (T,)
+        run_copies(toks, sweep=a.sweep, repeats=a.repeats)
+    sys.exit(0)
 if __name__ == "__main__" and "--sweep" in sys.argv:
     # where the row-streaming path hands over to the GEMM-layout grouped kernel (modules/fused/moe.py::ROWS_MAX_PAIRS)
     from autoawq_amd.modules.fused import moe as _m
