@@ -58,6 +58,13 @@ class AwqSampleProcArgs(ctypes.Structure):
                 ("history_stride", c_int64)]
 
 
+class AwqSampleRowsArgs(ctypes.Structure):
+    """struct AwqSampleRowsArgs of include/awq_hip.h (same field order): AwqSampleArgs with params / t as [B] arrays, then the
+    optional per-row processors and budgets."""
+    _fields_ = AwqSampleArgs._fields_ + [("proc", c_void_p), ("history", c_void_p), ("history_stride", c_int64),
+                                         ("max_new", c_void_p)]
+
+
 class AwqSpecParams(ctypes.Structure):
     """struct AwqSpecParams of include/awq_hip.h (same field order; lives in device memory)."""
     _fields_ = [("n_eos", ctypes.c_int32), ("pad", ctypes.c_int32), ("max_new_tokens", ctypes.c_int32),
@@ -150,6 +157,7 @@ SIGNATURES = {
     "awq_sample_tokens": (c_int, [ctypes.POINTER(AwqSampleArgs)]),
     "awq_sample_tokens_ex": (c_int, [ctypes.POINTER(AwqSampleArgs), ctypes.POINTER(AwqSampleProcArgs)]),
     "awq_sample_history_seed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "awq_sample_tokens_rows": (c_int, [ctypes.POINTER(AwqSampleRowsArgs)]),
     "awq_verify_attention_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "awq_verify_attention_splits": (c_int, [c_int64] * 5),
     "awq_verify_attention_rows": (c_int, [c_void_p] * 5 + [c_int64] * 7 + [c_float, c_void_p, c_size_t, c_void_p]),

@@ -49,6 +49,16 @@
 //   failed row included, as transformers' input_ids carry it; a pad outside [0, V) sets nothing), after every block of the row
 //   has read the history.  awq_sample_history_seed ORs an id matrix into a history (a prompt).
 // The PROC = false instantiations are the kernels of awq_sample_tokens, instruction for instruction.
+//
+// Rows form (awq_sample_tokens_rows, the ROWS template flag; pinned by tests/test_sampling_rows_cpu.py and
+// tests/test_gpu_sampling_rows.py): every row is a request of its own.  A block of row r reads params[r], t[r] and (PROC) proc[r]
+// -- indexed in device memory, never copied -- and the contract above holds with the row's values: greedy or sampled per row
+// (passes 2 and 3 return for a greedy row), Philox key (seed[r], 0) and counter (t[r], r, i / 4, 0), suppression while
+// t[r] <= min_new_tokens[r], ring[r * ring_cap + t[r] - 1], the row's EOS ids and pad.  t[r] is advanced by row r's own last
+// combine (finish_row), which runs after every block of the row has arrived, i.e. has read t[r]: no launch-wide step, WsHead is
+// not touched.  max_new (optional): with max_new[r] > 0 the row latches finished[r] in the launch that emits token index
+// t[r] >= max_new[r]; that token is real, the following ones are pad.
+// The ROWS = false instantiations are the kernels they were before the flag (DESIGN.md 3.10 states the comparison).
 #include "awq_device.h"
 #include "awq_internal.h"
 
@@ -117,7 +127,21 @@ struct ProcCtx : Ctx {
     uint32_t* history;
     int64_t history_stride;
 };
-template <bool PROC> using CtxT = typename std::conditional<PROC, ProcCtx, Ctx>::type;
+// The rows form (ROWS = true): params, t and proc point at [B] arrays; types of their own, so that the ROWS = false kernels keep
+// their argument layouts.
+struct RowsCtx : Ctx {
+    const int32_t* max_new;
+};
+struct RowsProcCtx : ProcCtx {
+    const int32_t* max_new;
+};
+template <bool PROC, bool ROWS = false>
+using CtxT = typename std::conditional<ROWS, typename std::conditional<PROC, RowsProcCtx, RowsCtx>::type,
+                                       typename std::conditional<PROC, ProcCtx, Ctx>::type>::type;
+
+// The parameters, token index and processors of a row: element `row` in the rows form, the one shared struct / word otherwise.
+// (An index that folds to 0 in the front end: accessor functions returning references changed the schedule of the ROWS = false pass 3.)
+#define AWQ_ROW_OF(ROWS, row) ((ROWS) ? (row) : 0)
 
 AWQ_DEV WsHead* head_of(const Ctx& c) { return reinterpret_cast<WsHead*>(c.ws); }
 AWQ_DEV RowWs* row_of(const Ctx& c, int r) { return reinterpret_cast<RowWs*>(c.ws + kHeadBytes + (size_t)r * kRowBytes); }
@@ -209,6 +233,7 @@ AWQ_DEV void load8(const Ctx& c, int row, int i0, uint32_t h[8]) {
 
 // The processors (PROC) on the 8 logits of this thread.  eos_on: t <= min_new_tokens (block-uniform).  The history bits of
 // i0 .. i0 + 7 are one byte (i0 % 8 == 0): bit v % 8 of byte v / 8 is bit v % 32 of word v / 32 (little endian).
+template <bool ROWS>
 AWQ_DEV void process8(const ProcCtx& c, const AwqSampleParams& P, int row, int i0, bool eos_on, uint32_t h[8]) {
     if (eos_on) {
         const int n = P.n_eos < 8 ? P.n_eos : 8;
@@ -219,7 +244,7 @@ AWQ_DEV void process8(const ProcCtx& c, const AwqSampleParams& P, int row, int i
                 if (d == j) h[j] = 0xFC00u;
         }
     }
-    const float p = c.proc->repetition_penalty;
+    const float p = c.proc[AWQ_ROW_OF(ROWS, row)].repetition_penalty;
     if (p == 1.f || i0 >= c.V) return;  // (p = 1: v * 1 and v / 1 are v, and fp16(float(h)) is h)
     const uint32_t bits = reinterpret_cast<const uint8_t*>(c.history + (int64_t)row * c.history_stride)[i0 >> 3];
     if (!bits) return;
@@ -234,7 +259,9 @@ AWQ_DEV void process8(const ProcCtx& c, const AwqSampleParams& P, int row, int i
 }
 
 // t <= min_new_tokens, read at block start
-AWQ_DEV bool eos_suppressed(const ProcCtx& c) { return ld(c.t) <= c.proc->min_new_tokens; }
+template <bool ROWS> AWQ_DEV bool eos_suppressed(const ProcCtx& c, int row) {
+    return ld(c.t + AWQ_ROW_OF(ROWS, row)) <= c.proc[AWQ_ROW_OF(ROWS, row)].min_new_tokens;
+}
 
 AWQ_DEV bool is_greedy(const AwqSampleParams& P, int forced) { return forced || P.do_sample == 0 || !(P.temperature > 0.f); }
 
@@ -269,12 +296,14 @@ AWQ_DEV void set_status(const Ctx& c, int row) {
 // from the logits (not the pad of a finished or failed row) -- only then can it latch `finished`.  Nothing written here is
 // read by another block of this launch (the next launch reads it), so the launch counter needs no fence; t is read, and
 // its load drained, before this row's add, and only the last add's row writes t.
-template <bool PROC>
-AWQ_DEV void finish_row(const CtxT<PROC>& c, int row, const AwqSampleParams& P, int64_t tok, bool sampled) {
+// ROWS: t is the row's own word t[row]; every block of the row has read it before arriving on the row counter, so this block (the
+// row's last) advances it here, and the launch counter is not used.  max_new: the row's budget latch.
+template <bool PROC, bool ROWS>
+AWQ_DEV void finish_row(const CtxT<PROC, ROWS>& c, int row, const AwqSampleParams& P, int64_t tok, bool sampled) {
     RowWs* w = row_of(c, row);
     const RowState zero{};
     w->st = zero;
-    const int32_t t = ld(c.t);
+    const int32_t t = ld(c.t + AWQ_ROW_OF(ROWS, row));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     c.out[row * c.out_stride] = tok;
     if (c.ring && t >= 1 && t <= c.ring_cap) c.ring[row * c.ring_cap + (t - 1)] = (int32_t)tok;
@@ -288,10 +317,18 @@ AWQ_DEV void finish_row(const CtxT<PROC>& c, int row, const AwqSampleParams& P, 
             __hip_atomic_fetch_or(c.history + row * c.history_stride + (tok >> 5), 1u << (tok & 31), __ATOMIC_RELAXED,
                                   __HIP_MEMORY_SCOPE_AGENT);
     }
-    WsHead* h = head_of(c);
-    if (__hip_atomic_fetch_add(&h->arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)c.B - 1) {
-        st(&h->arrive, 0u);
-        st(c.t, t + 1);
+    if constexpr (ROWS) {
+        if (c.finished && c.max_new) {
+            const int32_t m = c.max_new[row];
+            if (m > 0 && t >= m) c.finished[row] = 1;
+        }
+        st(c.t + row, t + 1);
+    } else {
+        WsHead* h = head_of(c);
+        if (__hip_atomic_fetch_add(&h->arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)c.B - 1) {
+            st(&h->arrive, 0u);
+            st(c.t, t + 1);
+        }
     }
 }
 
@@ -333,13 +370,13 @@ AWQ_DEV uint32_t find_from_top(Get get, unsigned long long base, Ok ok, unsigned
 }
 
 // ---- pass 1 ----------------------------------------------------------------------------------------------------------
-template <bool PROC>
-__global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC> c, int greedy_forced) {
+template <bool PROC, bool ROWS>
+__global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC, ROWS> c, int greedy_forced) {
     const int row = blockIdx.y, tid = threadIdx.x;
-    const AwqSampleParams& P = *c.params;  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
+    const AwqSampleParams& P = c.params[AWQ_ROW_OF(ROWS, row)];  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
     const bool greedy = is_greedy(P, greedy_forced);
     bool eos_on = false;
-    if constexpr (PROC) eos_on = eos_suppressed(c);
+    if constexpr (PROC) eos_on = eos_suppressed<ROWS>(c, row);
     RowWs* w = row_of(c, row);
     const bool fin = c.finished && c.finished[row] != 0;
     __shared__ uint32_t s_cnt[256];
@@ -352,7 +389,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC> c, int greed
         const int i0 = blockIdx.x * kChunk + tid * kPerThread;
         uint32_t h[8];
         load8(c, row, i0, h);
-        if constexpr (PROC) process8(c, P, row, i0, eos_on, h);
+        if constexpr (PROC) process8<ROWS>(c, P, row, i0, eos_on, h);
         unsigned long long best = 0;
         uint32_t bad = 0;
 #pragma unroll
@@ -399,7 +436,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC> c, int greed
     const bool live = !fin && !bad && best != 0;
     if (!fin && !live && tid == 0) set_status(c, row);
     if (greedy) {
-        if (tid == 0) finish_row<PROC>(c, row, P, live ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, live);
+        if (tid == 0) finish_row<PROC, ROWS>(c, row, P, live ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, live);
         return;
     }
     __shared__ uint32_t s_hist[256];
@@ -427,13 +464,13 @@ __global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC> c, int greed
 }
 
 // ---- pass 2 ----------------------------------------------------------------------------------------------------------
-template <bool PROC>
-__global__ __launch_bounds__(kThreads) void sample_pass2(CtxT<PROC> c, int greedy_forced) {
+template <bool PROC, bool ROWS>
+__global__ __launch_bounds__(kThreads) void sample_pass2(CtxT<PROC, ROWS> c, int greedy_forced) {
     const int row = blockIdx.y, tid = threadIdx.x;
-    const AwqSampleParams& P = *c.params;  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
+    const AwqSampleParams& P = c.params[AWQ_ROW_OF(ROWS, row)];  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
     if (is_greedy(P, greedy_forced)) return;
     bool eos_on = false;
-    if constexpr (PROC) eos_on = eos_suppressed(c);
+    if constexpr (PROC) eos_on = eos_suppressed<ROWS>(c, row);
     RowWs* w = row_of(c, row);
     const RowState S = w->st;
     const bool topp = P.top_p < 1.f;
@@ -449,7 +486,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass2(CtxT<PROC> c, int greed
         const int i0 = blockIdx.x * kChunk + tid * kPerThread;
         uint32_t h[8];
         load8(c, row, i0, h);
-        if constexpr (PROC) process8(c, P, row, i0, eos_on, h);
+        if constexpr (PROC) process8<ROWS>(c, P, row, i0, eos_on, h);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             if ((h[j] & 0x7FFFu) >= 0x7C00u) continue;
@@ -517,13 +554,13 @@ __global__ __launch_bounds__(kThreads) void sample_pass2(CtxT<PROC> c, int greed
 }
 
 // ---- pass 3 ----------------------------------------------------------------------------------------------------------
-template <bool PROC>
-__global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC> c, int greedy_forced) {
+template <bool PROC, bool ROWS>
+__global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC, ROWS> c, int greedy_forced) {
     const int row = blockIdx.y, tid = threadIdx.x;
-    const AwqSampleParams& P = *c.params;  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
+    const AwqSampleParams& P = c.params[AWQ_ROW_OF(ROWS, row)];  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
     if (is_greedy(P, greedy_forced)) return;
     bool eos_on = false;
-    if constexpr (PROC) eos_on = eos_suppressed(c);
+    if constexpr (PROC) eos_on = eos_suppressed<ROWS>(c, row);
     RowWs* w = row_of(c, row);
     const RowState S = w->st;
     const bool topp = S.bin_p != kNone && P.top_p < 1.f;
@@ -533,11 +570,11 @@ __global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC> c, int greed
     __syncthreads();
     if (S.mode == MODE_LIVE) {
         const float mx = key_to_float(S.maxkey), T = P.temperature;
-        const unsigned long long seed = P.seed, t = (unsigned long long)ld(c.t);
+        const unsigned long long seed = P.seed, t = (unsigned long long)ld(c.t + AWQ_ROW_OF(ROWS, row));
         const int i0 = blockIdx.x * kChunk + tid * kPerThread;
         uint32_t h[8];
         load8(c, row, i0, h);
-        if constexpr (PROC) process8(c, P, row, i0, eos_on, h);
+        if constexpr (PROC) process8<ROWS>(c, P, row, i0, eos_on, h);
         const uint32_t lo_key = topp ? (S.bin_p << 8) : S.tau_k;
         const uint32_t tau = lo_key > S.tau_k ? lo_key : S.tau_k;
         unsigned long long best = 0;
@@ -593,7 +630,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC> c, int greed
     if (tid == 0) st(&w->best_above, 0ull);
     if (tid >= 64) return;
     if (S.mode != MODE_LIVE) {
-        if (tid == 0) finish_row<PROC>(c, row, P, (int64_t)P.pad, false);
+        if (tid == 0) finish_row<PROC, ROWS>(c, row, P, (int64_t)P.pad, false);
         return;
     }
     uint32_t lo_p = 0;
@@ -611,7 +648,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC> c, int greed
     best = above_best > best ? above_best : best;
     if (tid == 0) {
         if (!best) set_status(c, row);
-        finish_row<PROC>(c, row, P, best ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, best != 0);
+        finish_row<PROC, ROWS>(c, row, P, best ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, best != 0);
     }
 }
 
@@ -624,10 +661,12 @@ size_t awq_sample_workspace_bytes(int64_t B, int64_t V) {
 
 namespace {
 
-// validation of the launch arguments shared by awq_sample_tokens and awq_sample_tokens_ex; AWQ_OK and *c filled, or the error
-int sample_ctx(const AwqSampleArgs* a, Ctx* c) {
+// validation of the launch arguments shared by awq_sample_tokens, awq_sample_tokens_ex and awq_sample_tokens_rows (A: AwqSampleArgs
+// or AwqSampleRowsArgs, which carries the same fields); AWQ_OK and *c filled, or the error
+template <typename A>
+int sample_ctx(const A* a, Ctx* c) {
     if (!a) return AWQ_ERR_NULL;
-    if (a->struct_bytes != sizeof(AwqSampleArgs)) return AWQ_ERR_BAD_SHAPE;
+    if (a->struct_bytes != sizeof(A)) return AWQ_ERR_BAD_SHAPE;
     if (a->B < 1 || a->B > kMaxRows || a->V < 1 || a->V > kMaxVocab) return AWQ_ERR_UNSUPPORTED;
     if (a->row_stride < a->V && a->B > 1) return AWQ_ERR_BAD_SHAPE;
     if (!a->logits || !a->params || !a->t || !a->out || !a->status || !a->workspace) return AWQ_ERR_NULL;
@@ -652,15 +691,15 @@ int sample_ctx(const AwqSampleArgs* a, Ctx* c) {
     return AWQ_OK;
 }
 
-template <bool PROC>
-int sample_run(const AwqSampleArgs* a, const CtxT<PROC>& c) {
+template <bool PROC, bool ROWS = false, typename A>
+int sample_run(const A* a, const CtxT<PROC, ROWS>& c) {
     const hipStream_t s = static_cast<hipStream_t>(a->stream);
     const int greedy = (a->flags & AWQ_SAMPLE_FLAG_GREEDY) != 0;
     const dim3 grid((unsigned)((a->V + kChunk - 1) / kChunk), (unsigned)a->B);
-    hipLaunchKernelGGL(sample_pass1<PROC>, grid, dim3(kThreads), 0, s, c, greedy);
+    hipLaunchKernelGGL((sample_pass1<PROC, ROWS>), grid, dim3(kThreads), 0, s, c, greedy);
     if (!greedy) {
-        hipLaunchKernelGGL(sample_pass2<PROC>, grid, dim3(kThreads), 0, s, c, 0);
-        hipLaunchKernelGGL(sample_pass3<PROC>, grid, dim3(kThreads), 0, s, c, 0);
+        hipLaunchKernelGGL((sample_pass2<PROC, ROWS>), grid, dim3(kThreads), 0, s, c, 0);
+        hipLaunchKernelGGL((sample_pass3<PROC, ROWS>), grid, dim3(kThreads), 0, s, c, 0);
     }
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
@@ -698,6 +737,29 @@ int awq_sample_tokens_ex(const AwqSampleArgs* a, const AwqSampleProcArgs* q) {
     c.history = q->history;
     c.history_stride = q->history_stride;
     return sample_run<true>(a, c);
+}
+
+int awq_sample_tokens_rows(const AwqSampleRowsArgs* a) {
+    RowsProcCtx c;
+    const int rc = sample_ctx(a, &c);
+    if (rc != AWQ_OK) return rc;
+    if (((uintptr_t)a->params & 7u) != 0 || ((uintptr_t)a->t & 3u) != 0 || ((uintptr_t)a->max_new & 3u) != 0)
+        return AWQ_ERR_BAD_ALIGNMENT;
+    if (a->max_new && !a->finished) return AWQ_ERR_NULL;  // the budget latch is a finished flag
+    c.max_new = a->max_new;
+    if (!a->proc && !a->history) {
+        RowsCtx r;
+        static_cast<Ctx&>(r) = c;
+        r.max_new = a->max_new;
+        return sample_run<false, true>(a, r);
+    }
+    if (!a->proc || !a->history) return AWQ_ERR_NULL;  // they go together
+    if (a->history_stride < (a->V + 31) / 32) return AWQ_ERR_BAD_SHAPE;
+    if (((uintptr_t)a->history & 3u) != 0 || ((uintptr_t)a->proc & 15u) != 0) return AWQ_ERR_BAD_ALIGNMENT;
+    c.proc = a->proc;
+    c.history = a->history;
+    c.history_stride = a->history_stride;
+    return sample_run<true, true>(a, c);
 }
 
 int awq_sample_history_seed(uint32_t* history, int64_t history_stride, const int64_t* ids, int64_t ids_stride, int64_t B,

@@ -65,7 +65,7 @@ import torch
 from ... import ops
 from ..._lib import AwqHipError
 from .model import StepPlan
-from .ragged import generate_tail, mask_runs, mask_runs_extend, pack_ids, unpack_rows
+from .ragged import generate_tail, generate_tail_rows, mask_runs, mask_runs_extend, pack_ids, unpack_rows
 
 
 class GraphedDecoder:
@@ -108,6 +108,9 @@ class GraphedDecoder:
         self.proc_gen_graphs = {}  # with the logit processors (repetition_penalty / min_new_tokens): keyed as gen_graphs
         self.row_proc_gen_graphs = {}  # ... and as row_gen_graphs
         self._gen = None  # generate's device words (allocated by its first call)
+        self.rows_gen_graphs = {}  # generate with per-row arguments: bucket bound -> (graph, logits): per-row positions + rows sampler
+        self._gen_rows = None      # ... and its device words (one AwqSampleParams / AwqSampleProc / t / max_new per row)
+        self._history_of_last = None  # the history the last `generate` kept up to date (None: it ran without the processors)
         self.spec_graphs = {}    # speculative decoding: (bucket bound, T) -> (graph, logits): verify step + argmax + accept + draft
         self.verify_graphs = {}  # (bucket bound, T) -> (graph, logits): the verify step alone (`verify`)
         self._spec = {}          # T -> the device words of the speculative path (allocated by its first use)
@@ -356,11 +359,16 @@ class GraphedDecoder:
         self._sync_host_state()
         return logits
 
-    def _advance_rows(self, greedy=None, proc=False):
-        """`_advance` in per-row mode: per-row rolls, the bucket of the largest position, the per-row graphs."""
+    def _advance_rows(self, greedy=None, proc=False, rows_sampler=False):
+        """`_advance` in per-row mode: per-row rolls, the bucket of the largest position, the per-row graphs.  rows_sampler: the
+        one family of generate with per-row arguments (the rows sampler, processors attached)."""
         self._roll_rows()
         bound = self.bucket(max(self.positions) + 1)
-        if greedy is None:
+        if rows_sampler:
+            if bound not in self.rows_gen_graphs:
+                self.rows_gen_graphs[bound] = self._capture(bound, sample=self._sample_rows, rows=True)
+            graph, logits = self.rows_gen_graphs[bound]
+        elif greedy is None:
             graph, logits = self.row_graphs.get(bound) or self._capture(bound, rows=True)
         else:
             key = (bound, bool(greedy))
@@ -421,6 +429,33 @@ class GraphedDecoder:
         ops.sample_launch(logits, g["params"], g["t"], self.tok.view(-1), g["status"], g["ws"], ring=g["ring"],
                           finished=g["finished"], greedy=greedy, proc=g["proc"] if proc else None,
                           history=g["history"] if proc else None)
+
+    def _gen_rows_state(self, vocab, cap):
+        """`_gen_state` for generate with per-row arguments: params / proc / t / max_new hold one element per row.  The addresses
+        are baked into `rows_gen_graphs`, dropped when the words are reallocated."""
+        g = self._gen_rows
+        if g is not None and g["vocab"] == vocab and g["ring"].shape[1] >= cap:
+            return g
+        with torch.inference_mode(False):
+            dev, B = self.device, self.batch
+            g = {"vocab": vocab,
+                 "params": torch.zeros((B, 64), dtype=torch.uint8, device=dev),
+                 "proc": torch.zeros((B, 16), dtype=torch.uint8, device=dev),
+                 "t": torch.ones(B, dtype=torch.int32, device=dev),
+                 "max_new": torch.zeros(B, dtype=torch.int32, device=dev),
+                 "ring": torch.zeros((B, max(int(cap), 256)), dtype=torch.int32, device=dev),
+                 "finished": torch.zeros(B, dtype=torch.int32, device=dev),
+                 "status": torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev),
+                 "ws": torch.zeros(ops.sample_workspace_bytes(B, vocab), dtype=torch.uint8, device=dev),
+                 "history": torch.zeros((B, ops.sample_history_words(vocab)), dtype=torch.int32, device=dev)}
+        self.rows_gen_graphs = {}
+        self._gen_rows = g
+        return g
+
+    def _sample_rows(self, logits):
+        g = self._gen_rows
+        ops.sample_launch_rows(logits, g["params"], g["t"], self.tok.view(-1), g["status"], g["ws"], ring=g["ring"],
+                               finished=g["finished"], proc=g["proc"], history=g["history"], max_new=g["max_new"])
 
     def _check(self, g):
         st = g["status"].cpu()
@@ -612,6 +647,69 @@ class GraphedDecoder:
         new = torch.where(keep, new, torch.full_like(new, pad))
         return torch.cat([input_ids.long(), new], dim=1)
 
+    def _generate_rows(self, input_ids, args, eos_token_id, pad_token_id, check_every, attention_mask, extend):
+        """generate with per-row arguments (see `generate`): every check of the arguments comes before the first launch."""
+        B = self.batch
+        max_rows = []
+        for r, m in enumerate(ops.per_row("max_new_tokens", args["max_new_tokens"], B)):
+            if isinstance(m, bool) or int(m) != m or int(m) < 1:
+                raise ValueError(f"row {r}: max_new_tokens must be an integer >= 1, got {m}")
+            max_rows.append(int(m))
+        if eos_token_id is None or isinstance(eos_token_id, int):
+            eos_rows = [[] if eos_token_id is None else [int(eos_token_id)]] * B
+        else:
+            eos_rows = [[int(e) for e in row] for row in ops._eos_rows(eos_token_id, B)]
+        params = ops.sample_params_rows(B, do_sample=args["do_sample"], temperature=args["temperature"], top_k=args["top_k"],
+                                        top_p=args["top_p"], seed=args["seed"], eos_ids=eos_rows, pad=pad_token_id)
+        proc_bytes = ops.sample_proc_params_rows(B, args["repetition_penalty"], args["min_new_tokens"])
+        n_max = max(max_rows)
+        idle = []
+        if extend:
+            logits, idle = self._extend_turn(input_ids, attention_mask)
+        else:
+            ragged = self._ragged(input_ids, attention_mask)
+            logits = self.prefill(input_ids, attention_mask if ragged is not None else None)
+            if ragged is not None:  # the first token of row b comes from its column start_b + L_b - 1
+                last = torch.tensor([s + n - 1 for s, n in zip(*ragged)], dtype=torch.int64, device=self.device)
+                logits = logits[torch.arange(B, device=self.device), last].unsqueeze(1).contiguous()
+            else:
+                self.seek_rows([self.position] * B)  # the rows family reads per-row positions
+        g = self._gen_rows_state(logits.shape[-1], n_max)
+        # reset every decoder-owned device word, outside any capture; every row's token index restarts at 1
+        g["params"].copy_(params)
+        g["proc"].copy_(proc_bytes)
+        g["max_new"].copy_(torch.tensor(max_rows, dtype=torch.int32))
+        g["t"].fill_(1)
+        g["ring"].zero_()
+        g["finished"].zero_()
+        if idle:  # nothing to process: the row starts finished and emits pads
+            g["finished"][torch.tensor(idle, device=self.device)] = 1
+        g["status"].zero_()
+        prev = self._history_of_last
+        if not extend or prev is None:
+            g["history"].zero_()  # (extend after a call that kept no history: the sampler knows this turn's ids only)
+        elif prev is not g["history"] and prev.shape == g["history"].shape:
+            g["history"].copy_(prev)  # the ids seen so far move along
+        ops.sample_history(input_ids, g["vocab"], out=g["history"])
+        self._history_of_last = g["history"]
+        self._sample_rows(logits)  # token 1, eagerly, into self.tok
+        n = 1
+        while n < n_max:
+            if n % check_every == 0 and self._check(g):
+                break
+            self.tail = None
+            self._advance_rows(rows_sampler=True)  # step on token n, sample token n + 1
+            n += 1
+        done = self._check(g)
+        new = g["ring"][:, :n]
+        lengths = [p - (n - 1) for p in self._row_positions()]
+        cache_rows, pending, real = generate_tail_rows(lengths, new.cpu().tolist(), eos_rows, max_rows, n, idle=idle)
+        self.tail = {"cache_rows": cache_rows, "pending": pending}
+        if done:  # stop where the longest row ended: drop the all-pad columns after it
+            n = max(1, min(n, max(real)))
+            new = new[:, :n]
+        return torch.cat([input_ids.long(), new.long()], dim=1)  # (rows past their end already hold their own pad)
+
     @torch.inference_mode()
     def generate(self, input_ids, max_new_tokens, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                  eos_token_id=None, pad_token_id=None, check_every=16, attention_mask=None, repetition_penalty=1.0,
@@ -640,10 +738,27 @@ class GraphedDecoder:
         (`tail`: its prompt and the real tokens it was fed; the pads fed to a finished row are dropped), the last token that call
         emitted without feeding it comes first, then the new tokens, in one `extend`.  A row with neither starts finished and
         emits pads.  The repetition-penalty history is kept and extended by the new ids.  Not with draft_tokens (ValueError);
-        the window is `extend`'s: no roll while the new tokens are appended."""
+        the window is `extend`'s: no roll while the new tokens are appended.
+        Per-row arguments: each of do_sample, temperature, top_k, top_p, seed, max_new_tokens, repetition_penalty and
+        min_new_tokens also takes a sequence of `batch` values, and eos_token_id a list of lists (one per row; None: no EOS id):
+        every row is a request of its own.  Such a call uses the sampler's rows form (ops.sample_tokens_rows) in one graph family
+        of its own (`rows_gen_graphs`: per-row positions, processors attached); row r's tokens are those of the call with row r's
+        values as scalars.  The loop runs to max(max_new_tokens); a row past its own limit is finished on the device and padded
+        with its pad (pad_token_id, default the row's first EOS id), and n is the longest row's count.  With extend=True every
+        row's token index restarts at 1.  Not with draft_tokens (ValueError).  All scalars: the path above, unchanged."""
         input_ids = input_ids.to(self.device)
         if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
             raise ValueError(f"input_ids must be [{self.batch}, prompt], got {tuple(input_ids.shape)}")
+        per_row = {"do_sample": do_sample, "temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed,
+                   "max_new_tokens": max_new_tokens, "repetition_penalty": repetition_penalty, "min_new_tokens": min_new_tokens}
+        eos_per_row = (eos_token_id is not None and ops.is_seq(eos_token_id)
+                       and any(e is None or ops.is_seq(e) for e in eos_token_id))
+        if eos_per_row or any(ops.is_seq(v) for v in per_row.values()):
+            if draft_tokens:
+                raise ValueError("generate: draft_tokens does not take per-row arguments (speculative decoding is one greedy "
+                                 "request per batch)")
+            return self._generate_rows(input_ids, per_row, eos_token_id, pad_token_id, max(1, int(check_every)), attention_mask,
+                                       extend)
         max_new_tokens, check_every = int(max_new_tokens), max(1, int(check_every))
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
@@ -683,6 +798,7 @@ class GraphedDecoder:
         if idle:  # nothing to process: the row starts finished and emits pads
             g["finished"][torch.tensor(idle, device=self.device)] = 1
         g["status"].zero_()
+        self._history_of_last = g["history"] if proc else None
         if proc:
             g["proc"].copy_(proc_bytes)
             if not extend:

@@ -85,6 +85,35 @@ def generate_tail(lengths, ring, eos, n, idle=()):
     return cache_rows, pending
 
 
+def generate_tail_rows(lengths, ring, eos_rows, max_rows, n, idle=()):
+    """generate_tail for a call with per-row arguments: row b has its own EOS ids eos_rows[b] and its own budget max_rows[b], and
+    the call sampled n = min(max(max_rows), where the host stopped) tokens for every row.  Returns (cache_rows, pending, real);
+    real[b]: the row's real tokens -- up to and including its first EOS id, at most max_rows[b].  A row that used up a budget
+    below n has fed its last token to a decode step; it is still handed back as pending with the cache row under it dead, which is
+    where a call with that budget for every row leaves it (the token is then fed again by the next turn's extend)."""
+    cache_rows, pending, reals = [], [], []
+    for b, L in enumerate(lengths):
+        row = [int(t) for t in ring[b][:n]]
+        if len(row) != n or n < 1:
+            raise ValueError(f"generate_tail_rows: row {b} of the ring holds {len(row)} tokens, n = {n}")
+        eos = set(int(e) for e in eos_rows[b])
+        m = min(int(max_rows[b]), n)
+        if b in idle:
+            real, by_eos = 0, True
+        else:
+            real = next((i + 1 for i, t in enumerate(row[:m]) if t in eos), None)
+            by_eos = real is not None
+            real = real if by_eos else m
+        if by_eos:
+            cache_rows.append(int(L) + min(real, n - 1))
+            pending.append(row[n - 1] if real == n else None)
+        else:
+            cache_rows.append(int(L) + real - 1)
+            pending.append(row[real - 1])
+        reals.append(real)
+    return cache_rows, pending, reals
+
+
 def _columns(starts, lengths, width, device):
     """[B, width] source column of each packed column: start_b + min(i, L_b - 1)"""
     i = torch.arange(width, device=device).view(1, -1)

@@ -1255,6 +1255,184 @@ def sample_tokens(logits, *, do_sample, temperature=1.0, top_k=0, top_p=1.0, see
     return out
 
 
+# ---- the sampler's rows form: per-row parameters and token indices (awq_sample_tokens_rows) ------------------------------------
+
+def is_seq(v):
+    if isinstance(v, torch.Tensor):
+        return v.dim() > 0
+    return hasattr(v, "__len__") and not isinstance(v, (str, bytes))
+
+
+def per_row(name, value, B):
+    """A per-row argument as a list of B values: a scalar is broadcast, a sequence (list, tuple, array, tensor) must hold B."""
+    if not is_seq(value):
+        return [value.item() if isinstance(value, torch.Tensor) else value] * B
+    vals = value.tolist() if hasattr(value, "tolist") else list(value)
+    if len(vals) != B:
+        raise ValueError(f"{name}: a sequence of {len(vals)} values for {B} rows")
+    return vals
+
+
+def _eos_rows(eos_ids, B):
+    """one tuple of ids for every row, or one tuple (or None) per row"""
+    if eos_ids is None:
+        return [()] * B
+    if not is_seq(eos_ids):
+        return [(int(eos_ids),)] * B
+    eos = list(eos_ids)
+    if not any(e is None or is_seq(e) for e in eos):
+        return [tuple(eos)] * B
+    if len(eos) != B:
+        raise ValueError(f"eos_ids: {len(eos)} per-row lists for {B} rows")
+    return [() if e is None else tuple(e) if is_seq(e) else (int(e),) for e in eos]
+
+
+def sample_params_rows(B, *, do_sample, temperature=1.0, top_k=0, top_p=1.0, seed=0, eos_ids=(), pad=None):
+    """sample_params for B rows: struct AwqSampleParams [B] as a CPU uint8 [B, 64] tensor the caller copies to the device.  Each
+    argument is a scalar (broadcast) or a sequence of B values; eos_ids one tuple, or one tuple per row; pad defaults per row
+    to the row's first EOS id.  The checks are sample_params'; a ValueError names the offending row.  Host only."""
+    B = int(B)
+    if B < 1:
+        raise ValueError(f"sample_params_rows: B must be >= 1, got {B}")
+    cols = {k: per_row(k, v, B) for k, v in (("do_sample", do_sample), ("temperature", temperature), ("top_k", top_k),
+                                              ("top_p", top_p), ("seed", seed), ("pad", pad))}
+    eos = _eos_rows(eos_ids, B)
+    out = torch.empty((B, ctypes.sizeof(_lib.AwqSampleParams)), dtype=torch.uint8)
+    for r in range(B):
+        try:
+            out[r] = sample_params(eos_ids=eos[r], **{k: v[r] for k, v in cols.items()})
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"row {r}: {e}") from None
+    return out
+
+
+def sample_proc_params_rows(B, repetition_penalty=1.0, min_new_tokens=0):
+    """sample_proc_params for B rows: struct AwqSampleProc [B] as a CPU uint8 [B, 16] tensor; scalars are broadcast.  A
+    ValueError names the offending row.  Host only."""
+    B = int(B)
+    if B < 1:
+        raise ValueError(f"sample_proc_params_rows: B must be >= 1, got {B}")
+    pen, mn = per_row("repetition_penalty", repetition_penalty, B), per_row("min_new_tokens", min_new_tokens, B)
+    out = torch.empty((B, ctypes.sizeof(_lib.AwqSampleProc)), dtype=torch.uint8)
+    for r in range(B):
+        try:
+            out[r] = sample_proc_params(pen[r], mn[r])
+        except (ValueError, TypeError) as e:
+            raise ValueError(f"row {r}: {e}") from None
+    return out
+
+
+def sample_launch_rows(logits, params, t, out, status, workspace, ring=None, finished=None, greedy=False, proc=None, history=None,
+                       max_new=None):
+    """sample_launch with every row a request of its own (awq_sample_tokens_rows): params (uint8 [B, 64], sample_params_rows)
+    and t (int32 [B], advanced per row by the launch) are read per row; proc (uint8 [B, 16], sample_proc_params_rows) with
+    history as in sample_launch; max_new (int32 [B], with finished): row r latches finished[r] in the launch that emits its
+    token index max_new[r] (<= 0: no limit).  greedy: argmax for every row in one launch.  No validation of the configuration,
+    no sync.  Capturable."""
+    rows, rs = _logits_rows(logits)
+    B, V = rows.shape
+    _require_gpu(rows, params, t, out, status, workspace, ring, finished, proc, history, max_new)
+    if (proc is None) != (history is None):
+        raise _lib.AwqHipError("sample_launch_rows: proc and history go together")
+    if history is not None and (history.dtype != torch.int32 or history.dim() != 2 or history.shape[0] != B
+                                or history.shape[1] < sample_history_words(V) or history.stride(1) != 1):
+        raise _lib.AwqHipError(f"sample_launch_rows: history must be int32 [{B}, >= {sample_history_words(V)}] with unit column stride")
+    if not params.is_contiguous() or params.numel() * params.element_size() < B * ctypes.sizeof(_lib.AwqSampleParams):
+        raise _lib.AwqHipError(f"sample_launch_rows: params must hold {B} x 64 contiguous bytes (sample_params_rows)")
+    if proc is not None and (not proc.is_contiguous() or proc.numel() * proc.element_size() < B * ctypes.sizeof(_lib.AwqSampleProc)):
+        raise _lib.AwqHipError(f"sample_launch_rows: proc must hold {B} x 16 contiguous bytes (sample_proc_params_rows)")
+    if out.numel() < B or status.numel() * 32 < B or (finished is not None and finished.numel() < B):
+        raise _lib.AwqHipError("sample_launch_rows: out / status / finished too small for the batch")
+    if ring is not None and (ring.dim() != 2 or ring.shape[0] != B or not ring.is_contiguous() or ring.dtype != torch.int32):
+        raise _lib.AwqHipError("sample_launch_rows: ring must be a contiguous int32 [B, cap] tensor")
+    if out.dtype != torch.int64 or (finished is not None and finished.dtype != torch.int32):
+        raise _lib.AwqHipError("sample_launch_rows: out int64 and finished int32 expected")
+    for name, w in (("t", t), ("max_new", max_new)):
+        if w is not None and (w.dtype != torch.int32 or w.numel() < B or not w.is_contiguous()):
+            raise _lib.AwqHipError(f"sample_launch_rows: {name} must be a contiguous int32 [{B}] tensor")
+    if max_new is not None and finished is None:
+        raise _lib.AwqHipError("sample_launch_rows: max_new latches `finished`: pass both")
+    a = _lib.AwqSampleRowsArgs()
+    a.struct_bytes = ctypes.sizeof(_lib.AwqSampleRowsArgs)
+    a.flags = SAMPLE_FLAG_GREEDY if greedy else 0
+    a.logits, a.B, a.V, a.row_stride = _ptr(rows), B, V, rs
+    a.params, a.t = _ptr(params), _ptr(t)
+    a.out, a.out_stride = _ptr(out), out.stride(0) if out.dim() else 1
+    a.ring, a.ring_cap = _ptr(ring), ring.shape[1] if ring is not None else 0
+    a.finished, a.status = _ptr(finished), _ptr(status)
+    a.workspace, a.workspace_bytes = _ptr(workspace), workspace.numel()
+    a.proc, a.history, a.history_stride = _ptr(proc), _ptr(history), history.stride(0) if history is not None else 0
+    a.max_new = _ptr(max_new)
+    with torch.cuda.device(rows.device):
+        a.stream = _stream()
+        rc = _lib.lib().awq_sample_tokens_rows(ctypes.byref(a))
+    _lib.check(rc, "awq_sample_tokens_rows")
+    return out
+
+
+def sample_tokens_rows(logits, *, do_sample, temperature=1.0, top_k=0, top_p=1.0, seed=0, t=1, eos_ids=(), pad=None, out=None,
+                       ring=None, finished=None, status=None, repetition_penalty=1.0, min_new_tokens=0, history=None,
+                       max_new_tokens=None):
+    """sample_tokens with every row a request of its own: each of do_sample, temperature, top_k, top_p, seed, pad,
+    repetition_penalty, min_new_tokens and max_new_tokens is a scalar (broadcast) or a sequence of B values, eos_ids one tuple or
+    one tuple per row, and t -- the 1-based index of the token each row generates -- an int, a sequence of B ints, or an int32 [B]
+    device tensor that the launch advances per row.  Row r's token is row r of sample_tokens on the same logits with row r's
+    values and t = t[r].  max_new_tokens (with `finished`): row r latches finished[r] with the token of index max_new_tokens[r].
+    Returns out (int64 [B]).  Status handling, history and the processors as in sample_tokens.  The loop of one's own over
+    slots that are refilled one by one: keep t, finished and history on the device and rewrite a slot's words when it takes a
+    new request."""
+    rows, _ = _logits_rows(logits)
+    B, V = rows.shape
+    params = sample_params_rows(B, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                eos_ids=eos_ids, pad=pad)
+    proc = sample_proc_params_rows(B, repetition_penalty, min_new_tokens)
+    pens, mins = per_row("repetition_penalty", repetition_penalty, B), per_row("min_new_tokens", min_new_tokens, B)
+    if any(float(p) != 1.0 for p in pens) and history is None:
+        raise ValueError("sample_tokens_rows: repetition_penalty needs a history of the ids seen (sample_history)")
+    use_proc = history is not None or any(int(m) > 0 for m in mins)
+    if not isinstance(t, torch.Tensor):
+        t_rows = [int(v) for v in per_row("t", t, B)]
+        for r, v in enumerate(t_rows):
+            if v < 1:
+                raise ValueError(f"row {r}: t is the 1-based token index, got {v}")
+    max_rows = None
+    if max_new_tokens is not None:
+        max_rows = [int(m) for m in per_row("max_new_tokens", max_new_tokens, B)]
+        if finished is None:
+            raise ValueError("sample_tokens_rows: max_new_tokens latches `finished`: pass a finished tensor")
+    ds, temps = per_row("do_sample", do_sample, B), per_row("temperature", temperature, B)
+    greedy = all(not d or float(T) <= 0 for d, T in zip(ds, temps))
+    _require_gpu(rows)
+    dev = rows.device
+    need = sample_workspace_bytes(B, V)
+    if need == 0:
+        err = _lib.AwqHipError(f"sample_tokens_rows: no kernel for B = {B}, V = {V} (limits B <= 1024, V <= 2^20)")
+        err.code = _lib.ERR_UNSUPPORTED
+        raise err
+    with torch.cuda.device(dev):
+        params_d = params.to(dev, non_blocking=False)
+        t_d = t if isinstance(t, torch.Tensor) else torch.tensor(t_rows, dtype=torch.int32, device=dev)
+        if out is None:
+            out = torch.empty(B, dtype=torch.int64, device=dev)
+        own_status = status is None
+        if own_status:
+            status = torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev)
+        ws = _sample_workspace(dev, need)
+        proc_d = hist = max_d = None
+        if use_proc:
+            proc_d = proc.to(dev, non_blocking=False)
+            hist = history if history is not None else torch.zeros((B, sample_history_words(V)), dtype=torch.int32, device=dev)
+        if max_rows is not None:
+            max_d = torch.tensor(max_rows, dtype=torch.int32, device=dev)
+        sample_launch_rows(rows, params_d, t_d, out, status, ws, ring=ring, finished=finished, greedy=greedy, proc=proc_d,
+                           history=hist, max_new=max_d)
+        if own_status:
+            bad = [r for r in range(B) if (int(status[r // 32].item()) >> (r % 32)) & 1] if bool(status.any()) else []
+            if bad:
+                raise _lib.AwqHipError(f"sample_tokens_rows: rows {bad} hold NaN / +inf logits or keep no token (emitted pad)")
+    return out
+
+
 # ---- speculative decoding: the verify step's attention (csrc/verify_attn.hip), acceptance and prompt-lookup drafts (csrc/spec.hip)
 
 _verify_workspaces = {}

@@ -695,6 +695,49 @@ AWQ_EXPORT int awq_sample_tokens_ex(const AwqSampleArgs* args, const AwqSamplePr
 AWQ_EXPORT int awq_sample_history_seed(uint32_t* history, int64_t history_stride, const int64_t* ids, int64_t ids_stride,
                                        int64_t B, int64_t S, int64_t V, void* stream);
 
+/* ---- the sampler with per-row parameters and token indices (csrc/sample.hip, the ROWS kernels) ------------------------------
+ * awq_sample_tokens_rows is awq_sample_tokens / awq_sample_tokens_ex with every row a request of its own, in the sense of the
+ * *_rows attention kernels: row r reads params[r], t[r] and -- when proc is given -- proc[r] from DEVICE memory, and everything
+ * the two blocks above say about a row holds with that row's values:
+ *   - greedy or sampled is decided per row (do_sample[r] == 0 or temperature[r] <= 0: argmax); temperature, top_k, top_p per row;
+ *   - the Philox call of row r is key (seed[r], 0), counter (t[r], r, i / 4, 0);
+ *   - EOS ids and pad are the row's own; EOS suppression while t[r] <= min_new_tokens[r], the penalty repetition_penalty[r];
+ *   - ring[r * ring_cap + t[r] - 1] = token (1 <= t[r] <= ring_cap, else no ring write, as in the shared form);
+ *   - row r's own last block advances t[r] by one, after every block of the row has read it (there is no launch-wide step); a
+ *     finished row emits its pad and keeps advancing t[r].
+ * So row r's token is the token row r of the shared launch emits on the same logits with params[r], proc[r] and *t = t[r].
+ * max_new (optional; needs finished): with max_new[r] > 0 the row latches finished[r] in the launch that emits token index
+ * t[r] >= max_new[r] -- that token is real (the row's last), later ones are pad.  max_new[r] <= 0: no limit for the row.
+ * proc and history are given together (both NULL: no processors, the kernels of awq_sample_tokens with the row index added).
+ * AWQ_SAMPLE_FLAG_GREEDY keeps its meaning: one launch, argmax for every row.  Limits, validation order and error codes are
+ * those of awq_sample_tokens (then those of awq_sample_tokens_ex for proc / history); params 8-byte, proc 16-byte, t and
+ * max_new 4-byte aligned (AWQ_ERR_BAD_ALIGNMENT).  The workspace is the shared form's (awq_sample_workspace_bytes) and is left all zero. */
+typedef struct AwqSampleRowsArgs {
+    uint32_t struct_bytes; /* sizeof(AwqSampleRowsArgs) */
+    uint32_t flags;
+    const uint16_t* logits;
+    int64_t B;
+    int64_t V;
+    int64_t row_stride;    /* elements */
+    const AwqSampleParams* params; /* [B] */
+    int32_t* t;            /* [B] */
+    int64_t* out;
+    int64_t out_stride;    /* elements */
+    int32_t* ring;         /* [B, ring_cap] or NULL */
+    int64_t ring_cap;
+    int32_t* finished;     /* [B] or NULL */
+    uint32_t* status;      /* [ceil(B / 32)] */
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+    const AwqSampleProc* proc; /* [B] or NULL */
+    uint32_t* history;     /* [B, history_stride] or NULL (with proc) */
+    int64_t history_stride; /* words */
+    const int32_t* max_new; /* [B] or NULL */
+} AwqSampleRowsArgs;
+
+AWQ_EXPORT int awq_sample_tokens_rows(const AwqSampleRowsArgs* args);
+
 /* ---- speculative decoding: a k-token verify step (csrc/verify_attn.hip) and prompt-lookup drafts (csrc/spec.hip) ---------------
  * awq_verify_attention_rows: attention of T = 2 .. 8 NEW tokens per sequence over the cache, at per-row device positions.
  *   q [B, T, n_heads, 128] fp16 is the q_out of awq_rope_kv_append_rows(S = T), which has ALREADY written cache rows
