@@ -21,32 +21,56 @@ ONCE and replayed:
     for _ in range(n):
         logits = dec.step(next_ids)           # [batch, 1, vocab]; valid until the next step
 
-Token generation (`generate`) replays a second family of graphs: the same step, then the sampler (csrc/sample.hip) writing
-the next ids straight into the step's input buffer, a ring of generated tokens and the per-row finished flags.  The host only
-picks buckets, rolls the window and looks at the flags every `check_every` tokens.
+Every mode below goes through ONE driver.  A graph lives in a family -- a dict keyed by the bucket bound, and by whatever else is
+baked into the graph -- and is made on first use: `_graph(family, key, ...)` is the one get-or-capture, `_capture` the one capture
+skeleton (warm-up outside the capture, capture on the decoder's stream, the caller's stream fenced on both sides), `_replay` the
+one fenced replay.  `_advance` is the one token step behind `step`, `replay` and `generate`: roll a full window, pick the bound,
+pick family and key, replay, advance the host's position(s).  Shared and per-row mode differ there in the roll, the bound and
+the advance alone.  `_first_logits` is what every `generate` does up to token 1's logits, and `_generate_loop` the one loop
+behind the scalar call and the call with per-row arguments.  The families, what selects them and what their graphs hold:
+
+    graphs[bound]                           row_graphs[bound]              step / replay                     the step
+    gen_graphs[(bound, greedy)]             row_gen_graphs[...]            generate                          step + sampler
+    proc_gen_graphs[(bound, greedy)]        row_proc_gen_graphs[...]       ... repetition_penalty /          step + sampler with the
+                                                                           min_new_tokens                    logit processors
+                                            rows_gen_graphs[bound]         generate, per-row arguments       step + rows sampler
+                                            spec_graphs[(bound, T)]        generate(draft_tokens=T - 1)      verify step + argmax +
+                                                                                                             accept + draft
+                                            verify_graphs[(bound, T)]      verify                            verify step
+    (left: one shared position, the words `pos` / `len`; right: per-row positions, `pos_rows` / `len_rows`)
+
+The graphs bake in the addresses of the device words their sampler reads, so a family lives as long as its words: `_gen_state`
+drops the four scalar generation families when it reallocates (a longer ring, another vocabulary), its per-row form drops
+`rows_gen_graphs`, `_spec_state(T)` the speculative graphs of that T.
+
+Token generation (`generate`): the same step, then the sampler (csrc/sample.hip) writing the next ids straight into the step's
+input buffer, a ring of generated tokens and the per-row finished flags.  The host only picks buckets, rolls the window and looks
+at the flags every `check_every` tokens.
 
     out = dec.generate(prompt_ids, max_new_tokens=64, do_sample=True, top_p=0.9, seed=1)   # [batch, prompt + n] int64
 
 Prompts of different lengths come as one padded batch with an `attention_mask` (transformers' convention; modules/fused/
-ragged.py).  Every row then has its own position: `pos_rows` / `len_rows` hold one word per row, a second family of graphs
-(`row_graphs`, `row_gen_graphs`) reads them through the *_rows kernels, the host keeps one position per row (`positions`),
-picks the bucket from the largest and rolls a row's window on its own when that row alone would run past it.  No mask, or
-an all-ones mask, takes the shared words and the graphs above unchanged.
+ragged.py).  Every row then has its own position: `pos_rows` / `len_rows` hold one word per row, the per-row families read them
+through the *_rows kernels, the host keeps one position per row (`positions`), picks the bucket from the largest and rolls a
+row's window on its own when that row alone would run past it.  No mask, or an all-ones mask, takes the shared words and graphs.
 
     out = dec.generate(ids, attention_mask=mask, max_new_tokens=64)   # left-padded ids: transformers' layout
 
 repetition_penalty / min_new_tokens (transformers' logit processors) run inside the sampler's passes, reading a per-row bitmap of
-the ids seen so far that the sampler itself extends: a third and fourth family of generation graphs (`proc_gen_graphs`,
-`row_proc_gen_graphs`).  With both at their defaults generate takes the graphs above, unchanged.
+the ids seen so far that the sampler itself extends.  With both at their defaults the sampler is launched without them: the
+kernels that read neither.
+
+Per-row arguments (a sequence of `batch` values for a sampling argument, a list of lists for eos_token_id): every row is a request
+of its own.  One family, the sampler's rows form with the processors always attached, device words of its own (`_gen_rows`).
 
 Speculative decoding (`generate(draft_tokens=K)`, `verify` / `advance_rows`): one pass over the weights for T = K + 1 tokens per
-row.  A graph of the family `spec_graphs[(bound, T)]` runs the model on tok [B, T] at the per-row positions (rope + append of T
-rows, csrc/verify_attn.hip), takes the greedy argmax of every slot with the sampler, keeps the longest run of drafts the model
-agrees with (awq_spec_accept: ring, history, positions and finished flags advance on the device by what was accepted) and
-writes the next step's drafts by prompt lookup in the row's own history (awq_ngram_draft).  Rejected drafts leave cache rows at
-and above the row's new position; the next step's append overwrites them, nothing is rolled back.  The host only bounds the
-positions between checks.  `verify_graphs[(bound, T)]` is the same step without the two integer kernels, for callers with
-drafts of their own.  draft_tokens=0 (the default) creates none of this.
+row.  A graph of `spec_graphs` runs the model on tok [B, T] at the per-row positions (rope + append of T rows,
+csrc/verify_attn.hip), takes the greedy argmax of every slot with the sampler, keeps the longest run of drafts the model agrees
+with (awq_spec_accept: ring, history, positions and finished flags advance on the device by what was accepted) and writes the next
+step's drafts by prompt lookup in the row's own history (awq_ngram_draft).  Rejected drafts leave cache rows at and above the
+row's new position; the next step's append overwrites them, nothing is rolled back.  The host only bounds the positions between
+checks, and its loop stays its own (`_generate_spec`): a replay emits a variable number of tokens.  `verify_graphs` is the same
+step without the two integer kernels, for callers with drafts of their own.  draft_tokens=0 (the default) creates none of this.
 
     out = dec.generate(ids, max_new_tokens=128, draft_tokens=3, draft_ngram=3)   # the text of the plain greedy run
     dec.last_spec                                                                 # {"replays": r, "new_tokens": [n_b ...]}
@@ -55,7 +79,7 @@ Prefill at per-row positions (`extend`, `reset_rows`, `generate(extend=True)`): 
 tokens at ITS position (rope + append with per-row counts, then csrc/prefill_attn.hip's rows form) and leaves the decoder in
 per-row mode; a row with an all-zero mask is untouched.  `reset_rows` sends rows back to position 0 and keeps the others: a
 finished row's slot takes a new prompt while its neighbours go on.  `generate` records what it left in the caches per row (`tail`:
-modules/fused/ragged.py, generate_tail), and a following `generate(extend=True)` continues from there instead of restarting.
+modules/fused/ragged.py, generate_tail_rows), and a following `generate(extend=True)` continues from there instead of restarting.
 
     out1 = dec.generate(turn1, max_new_tokens=64, eos_token_id=eos)
     out2 = dec.generate(turn2, max_new_tokens=64, eos_token_id=eos, extend=True)   # turn 1 is not prefilled again
@@ -65,7 +89,7 @@ import torch
 from ... import ops
 from ..._lib import AwqHipError
 from .model import StepPlan
-from .ragged import generate_tail, generate_tail_rows, mask_runs, mask_runs_extend, pack_ids, unpack_rows
+from .ragged import generate_tail_rows, mask_runs, mask_runs_extend, pack_ids, unpack_rows
 
 
 class GraphedDecoder:
@@ -284,39 +308,86 @@ class GraphedDecoder:
         last = torch.tensor([max(n - 1, 0) for n in counts], dtype=torch.int64, device=self.device)
         return logits[torch.arange(B, device=self.device), last].unsqueeze(1).contiguous(), idle
 
-    # ---- one token ------------------------------------------------------------------------------------------------------
+    def _first_logits(self, input_ids, attention_mask, extend=False, per_row=False):
+        """What every generate path does up to token 1's logits: `_extend_turn`, or prefill and -- for prompts of different
+        lengths -- the gather of each row's last real column.  Returns (logits, the rows with nothing to process).  Unpadded
+        input leaves the positions shared unless per_row: then every row gets a position of its own, the one they share."""
+        if extend:
+            return self._extend_turn(input_ids, attention_mask)
+        ragged = self._ragged(input_ids, attention_mask)
+        logits = self.prefill(input_ids, attention_mask if ragged is not None else None)
+        if ragged is not None:  # the first token of row b comes from its column start_b + L_b - 1
+            last = torch.tensor([s + n - 1 for s, n in zip(*ragged)], dtype=torch.int64, device=self.device)
+            logits = logits[torch.arange(self.batch, device=self.device), last].unsqueeze(1).contiguous()
+        elif per_row:
+            self.seek_rows([self.position] * self.batch)
+        return logits, []
+
+    # ---- one driver: capture, look-up, replay, advance -----------------------------------------------------------------------
     @torch.inference_mode()
-    def _capture(self, bound, sample=None, rows=False):
+    def _capture(self, bound, rows, body, advance):
+        """The one capture skeleton -> (graph, logits).  body(capturing) runs the model on the decoder's static ids and returns
+        the logits: once eagerly (the warm-up: it appends cache rows at the current positions, which the first replay writes
+        again with the real tokens, and builds every lazily cached buffer OUTSIDE the capture), once recorded.  What moves the
+        decoder's words belongs under `capturing` alone.  rows: the blocks read pos_rows / len_rows.  advance: the recorded step
+        also moves its position words on by one, and they are restored from clones afterwards."""
         pos, ln = (self.pos_rows, self.len_rows) if rows else (self.pos, self.len)
         for b in self.blocks:
             b.attn.use_device_positions(pos, ln, per_row=rows)
             b.attn.decode_len_bound = bound
-        keep = (pos.clone(), ln.clone())
+        keep = (pos.clone(), ln.clone()) if advance else None
         caller = torch.cuda.current_stream(self.device)  # (taken BEFORE entering the decoder's stream: the ids were copied on it)
         with torch.cuda.stream(self.stream):
             self.stream.wait_stream(caller)
-            # (the warm-up step runs the kernels for real -- it appends a row at the current position, which the first replay
-            #  writes again with the real token -- and builds every lazily cached buffer OUTSIDE the capture)
-            self.lm(self.tok)
-            self._sync_host_state()
+            body(False)
+            self._sync_host_state()  # (the model's eager step moved the blocks' host bookkeeping; a verify step did not: a no-op there)
             self.stream.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=self.stream):
-                logits = self.lm(self.tok)
-                if sample is not None:
-                    sample(logits)
-                pos.add_(1)
-                ln.add_(1)
+                logits = body(True)
+                if advance:
+                    pos.add_(1)
+                    ln.add_(1)
             self.stream.synchronize()
-            pos.copy_(keep[0])
-            ln.copy_(keep[1])
+            if advance:
+                pos.copy_(keep[0])
+                ln.copy_(keep[1])
         caller.wait_stream(self.stream)
         self._sync_host_state()
-        if sample is not None:
-            return graph, logits
-        graphs = self.row_graphs if rows else self.graphs
-        graphs[bound] = (graph, logits)
-        return graphs[bound]
+        return graph, logits
+
+    def _step_body(self, capturing, sample):
+        logits = self.lm(self.tok)
+        if capturing and sample is not None:
+            sample(logits)
+        return logits
+
+    def _spec_body(self, capturing, st, full):
+        """the verify step; full: + argmax, and -- recorded only, they move the decoder's words -- accept and draft"""
+        logits = self.lm.verify(st["tok"])
+        if full:
+            self._spec_tail(st, logits)
+            if capturing:
+                ops.spec_accept(st["params"], st["tok"], st["pred"], st["hist"], st["n_hist"], st["cnt"], st["ring"],
+                                st["finished"], self.pos_rows, self.len_rows, status=st["status"], steps=st["steps"])
+                ops.ngram_draft(st["params"], st["tok"], st["hist"], st["n_hist"])
+        return logits
+
+    def _graph(self, family, key, bound, rows, advance, body, *args):
+        """The one get-or-capture: family[key] = (graph, logits), captured on first use from body(capturing, *args) under the
+        bucket bound `bound`."""
+        entry = family.get(key)
+        if entry is None:
+            entry = family[key] = self._capture(bound, rows, lambda capturing: body(capturing, *args), advance)
+        return entry
+
+    def _replay(self, graph):
+        """one replay on the decoder's stream, fenced against the caller's work on both sides"""
+        caller = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(caller)   # the ids were copied on the caller's stream
+        with torch.cuda.stream(self.stream):
+            graph.replay()
+        caller.wait_stream(self.stream)   # ... and the caller reads the logits
 
     def _roll_rows(self):
         """Per-row mode: every row that alone would run past the window forgets its oldest StepPlan.ROLL positions, as
@@ -331,57 +402,32 @@ class GraphedDecoder:
             self.positions[r] -= n
         self.seek_rows(self.positions)
 
-    def _advance(self, greedy=None, proc=False):
-        """What `step` and `replay` share: roll a full window, pick (or capture) the bucket's graph, replay it on the decoder's stream
-        between the caller's work, advance the position on the host as the graph did on the device.  greedy = True / False:
-        the generation graph (step + sampler) instead of the step graph; proc: the one whose sampler runs the logit processors."""
+    def _advance(self, shared, per_row, tag=None, sample=None):
+        """One token, for `step`, `replay` and the generate loop: roll a full window, pick (or capture) the bucket's graph, replay
+        it, advance the position(s) on the host as the graph did on the device.  shared / per_row: the family of the mode at one
+        shared position and at per-row positions (shared None: the mode runs at per-row positions only); tag: what follows the
+        bound in its keys (None: the bound alone); sample: the sampler call recorded behind the step (None: the step graphs).
+        Shared and per-row mode differ in the roll, the bound and the host's advance."""
         self.tail = None  # (generate states it again when it is done)
-        if self.positions is not None:
-            return self._advance_rows(greedy, proc)
-        if self.position + 1 > self.max_seq_len:  # past the window: forget the oldest positions (eagerly)
-            live = [b.attn.cache.roll_kv_n_steps(self.position, n=StepPlan.ROLL) for b in self.blocks][0]
-            self.seek(live)
-        bound = self.bucket(self.position + 1)
-        if greedy is None:
-            graph, logits = self.graphs.get(bound) or self._capture(bound)
+        rows = self.positions is not None
+        if rows:
+            self._roll_rows()
+            bound, family = self.bucket(max(self.positions) + 1), per_row
         else:
-            key = (bound, bool(greedy))
-            family = self.proc_gen_graphs if proc else self.gen_graphs
-            if key not in family:
-                family[key] = self._capture(bound, sample=lambda lg: self._sample(lg, greedy, proc))
-            graph, logits = family[key]
-        caller = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(caller)   # the ids were copied on the caller's stream
-        with torch.cuda.stream(self.stream):
-            graph.replay()
-        caller.wait_stream(self.stream)   # ... and the caller reads the logits
-        self.position += 1
-        self._sync_host_state()
-        return logits
-
-    def _advance_rows(self, greedy=None, proc=False, rows_sampler=False):
-        """`_advance` in per-row mode: per-row rolls, the bucket of the largest position, the per-row graphs.  rows_sampler: the
-        one family of generate with per-row arguments (the rows sampler, processors attached)."""
-        self._roll_rows()
-        bound = self.bucket(max(self.positions) + 1)
-        if rows_sampler:
-            if bound not in self.rows_gen_graphs:
-                self.rows_gen_graphs[bound] = self._capture(bound, sample=self._sample_rows, rows=True)
-            graph, logits = self.rows_gen_graphs[bound]
-        elif greedy is None:
-            graph, logits = self.row_graphs.get(bound) or self._capture(bound, rows=True)
+            if self.position + 1 > self.max_seq_len:  # past the window: forget the oldest positions (eagerly)
+                live = [b.attn.cache.roll_kv_n_steps(self.position, n=StepPlan.ROLL) for b in self.blocks][0]
+                self.seek(live)
+            bound, family = self.bucket(self.position + 1), shared
+        key = bound if tag is None else (bound, tag)
+        entry = family.get(key)  # (once per token: the hit costs one dict look-up, `_graph` is entered on a miss alone)
+        if entry is None:
+            entry = self._graph(family, key, bound, rows, True, self._step_body, sample)
+        graph, logits = entry
+        self._replay(graph)
+        if rows:
+            self.positions = [p + 1 for p in self.positions]
         else:
-            key = (bound, bool(greedy))
-            family = self.row_proc_gen_graphs if proc else self.row_gen_graphs
-            if key not in family:
-                family[key] = self._capture(bound, sample=lambda lg: self._sample(lg, greedy, proc), rows=True)
-            graph, logits = family[key]
-        caller = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(caller)
-        with torch.cuda.stream(self.stream):
-            graph.replay()
-        caller.wait_stream(self.stream)
-        self.positions = [p + 1 for p in self.positions]
+            self.position += 1
         self._sync_host_state()
         return logits
 
@@ -390,72 +436,53 @@ class GraphedDecoder:
         """token_ids [batch, 1] (or [batch]): the tokens at the current position.  Returns the logits [batch, 1, vocab] -- the
         graph's static output buffer, overwritten by the next step."""
         self.tok.copy_(token_ids.reshape(self.batch, 1))
-        return self._advance()
+        return self._advance(self.graphs, self.row_graphs)
 
     @torch.inference_mode()
     def replay(self):
         """The current bucket's graph once more on the decoder's stream with the ids already in place (benchmarks: no host
         copies in the timed region).  Same roll / stream / host bookkeeping as `step`."""
-        return self._advance()
+        return self._advance(self.graphs, self.row_graphs)
 
     # ---- generation: sampler in the graph ---------------------------------------------------------------------------------
-    def _gen_state(self, vocab, cap):
-        """The device words generate owns.  Their addresses are baked into the generation graphs: reallocated (and the graphs
-        dropped) only when the vocabulary or the ring capacity has to grow.  history: the ids seen per row (bit v % 32 of word
-        v / 32), proc: struct AwqSampleProc -- the logit processors' state."""
-        g = self._gen
-        if g is not None and g["vocab"] == vocab and g["ring"].shape[1] >= cap:
-            return g
-        with torch.inference_mode(False):
-            dev = self.device
-            g = {"vocab": vocab,
-                 "params": torch.zeros(64, dtype=torch.uint8, device=dev),
-                 "t": torch.ones(1, dtype=torch.int32, device=dev),
-                 "ring": torch.zeros((self.batch, max(int(cap), 256)), dtype=torch.int32, device=dev),
-                 "finished": torch.zeros(self.batch, dtype=torch.int32, device=dev),
-                 "status": torch.zeros((self.batch + 31) // 32, dtype=torch.int32, device=dev),
-                 "ws": torch.zeros(ops.sample_workspace_bytes(self.batch, vocab), dtype=torch.uint8, device=dev),
-                 "history": torch.zeros((self.batch, ops.sample_history_words(vocab)), dtype=torch.int32, device=dev),
-                 "proc": torch.zeros(16, dtype=torch.uint8, device=dev)}
-        self.gen_graphs = {}
-        self.row_gen_graphs = {}
-        self.proc_gen_graphs = {}
-        self.row_proc_gen_graphs = {}
-        self._gen = g
-        return g
-
-    def _sample(self, logits, greedy, proc=False):
-        g = self._gen
-        ops.sample_launch(logits, g["params"], g["t"], self.tok.view(-1), g["status"], g["ws"], ring=g["ring"],
-                          finished=g["finished"], greedy=greedy, proc=g["proc"] if proc else None,
-                          history=g["history"] if proc else None)
-
-    def _gen_rows_state(self, vocab, cap):
-        """`_gen_state` for generate with per-row arguments: params / proc / t / max_new hold one element per row.  The addresses
-        are baked into `rows_gen_graphs`, dropped when the words are reallocated."""
-        g = self._gen_rows
+    def _gen_state(self, vocab, cap, per_row=False):
+        """The device words generate owns (per_row: of generate with per-row arguments -- params / proc / t hold one element per
+        row, and max_new).  Their addresses are baked into the generation graphs: reallocated (and those graphs dropped) only when
+        the vocabulary or the ring capacity has to grow.  history: the ids seen per row (bit v % 32 of word v / 32), proc: struct
+        AwqSampleProc -- the logit processors' state."""
+        g = self._gen_rows if per_row else self._gen
         if g is not None and g["vocab"] == vocab and g["ring"].shape[1] >= cap:
             return g
         with torch.inference_mode(False):
             dev, B = self.device, self.batch
+            one = (B,) if per_row else ()  # one parameter word per row, or one for all
             g = {"vocab": vocab,
-                 "params": torch.zeros((B, 64), dtype=torch.uint8, device=dev),
-                 "proc": torch.zeros((B, 16), dtype=torch.uint8, device=dev),
-                 "t": torch.ones(B, dtype=torch.int32, device=dev),
-                 "max_new": torch.zeros(B, dtype=torch.int32, device=dev),
+                 "params": torch.zeros(one + (64,), dtype=torch.uint8, device=dev),
+                 "proc": torch.zeros(one + (16,), dtype=torch.uint8, device=dev),
+                 "t": torch.ones(B if per_row else 1, dtype=torch.int32, device=dev),
                  "ring": torch.zeros((B, max(int(cap), 256)), dtype=torch.int32, device=dev),
                  "finished": torch.zeros(B, dtype=torch.int32, device=dev),
                  "status": torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev),
                  "ws": torch.zeros(ops.sample_workspace_bytes(B, vocab), dtype=torch.uint8, device=dev),
                  "history": torch.zeros((B, ops.sample_history_words(vocab)), dtype=torch.int32, device=dev)}
-        self.rows_gen_graphs = {}
-        self._gen_rows = g
+            if per_row:
+                g["max_new"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        if per_row:
+            self.rows_gen_graphs = {}
+            self._gen_rows = g
+        else:
+            self.gen_graphs = {}
+            self.row_gen_graphs = {}
+            self.proc_gen_graphs = {}
+            self.row_proc_gen_graphs = {}
+            self._gen = g
         return g
 
-    def _sample_rows(self, logits):
-        g = self._gen_rows
-        ops.sample_launch_rows(logits, g["params"], g["t"], self.tok.view(-1), g["status"], g["ws"], ring=g["ring"],
-                               finished=g["finished"], proc=g["proc"], history=g["history"], max_new=g["max_new"])
+    def _sample(self, logits, g, per_row, greedy, proc):
+        """the sampler on the words g, writing the next ids into the step's input buffer; per_row: g holds per-row words (the rows form)"""
+        launch, more = (ops.sample_launch_rows, {"max_new": g["max_new"]}) if per_row else (ops.sample_launch, {})
+        launch(logits, g["params"], g["t"], self.tok.view(-1), g["status"], g["ws"], ring=g["ring"], finished=g["finished"],
+               greedy=greedy, proc=g["proc"] if proc else None, history=g["history"] if proc else None, **more)
 
     def _check(self, g):
         st = g["status"].cpu()
@@ -463,6 +490,72 @@ class GraphedDecoder:
             bad = [r for r in range(self.batch) if (int(st[r // 32]) >> (r % 32)) & 1]
             raise AwqHipError(f"generate: rows {bad} produced NaN / +inf logits or kept no token")
         return bool(g["finished"].cpu().all())
+
+    def _generate_loop(self, input_ids, logits, idle, extend, check_every, mode):
+        """The one generate loop, from token 1's logits to the ids returned.  mode describes the call: g (its device words), words
+        (name -> the CPU bytes this call puts into them), sample (the sampler call: eagerly for token 1, recorded behind the
+        step), advance (`_advance`'s two families -- taken after `_gen_state`, which may replace them -- and its tag), eos /
+        budgets (one list of EOS ids and one max_new_tokens per row), and per_row / proc / moved for the three places where the
+        scalar call and the call with per-row arguments differ."""
+        g, sample, eos_rows, budgets = mode["g"], mode["sample"], mode["eos"], mode["budgets"]
+        shared, rows_family, tag = mode["advance"]
+        # reset every decoder-owned device word, outside any capture; every token index restarts at 1
+        for name, value in mode["words"].items():
+            g[name].copy_(value)
+        g["t"].fill_(1)
+        g["ring"].zero_()
+        g["finished"].zero_()
+        if idle:  # nothing to process: the row starts finished and emits pads
+            g["finished"][torch.tensor(idle, device=self.device)] = 1
+        g["status"].zero_()
+        # History carry-over under extend differs between the two calls, and stays so.
+        if mode["per_row"]:
+            # per-row arguments: the processors always run, and what moves along is the history the LAST generate kept up to
+            # date, whichever words it lives in (none: the sampler knows this turn's ids only)
+            prev = self._history_of_last
+            if not extend or prev is None:
+                g["history"].zero_()
+            elif prev is not g["history"] and prev.shape == g["history"].shape:
+                g["history"].copy_(prev)
+            ops.sample_history(input_ids, g["vocab"], out=g["history"])
+            self._history_of_last = g["history"]
+        else:
+            # scalars: the history is touched only when the processors are on; under extend it stays as it is in these words, or
+            # comes from the words this call replaced (`moved`: reallocated for a longer ring, same vocabulary)
+            self._history_of_last = g["history"] if mode["proc"] else None
+            if mode["proc"]:
+                if not extend:
+                    g["history"].zero_()
+                elif mode["moved"] is not None:
+                    g["history"].copy_(mode["moved"])
+                ops.sample_history(input_ids, g["vocab"], out=g["history"])
+        sample(logits)  # token 1, eagerly, into self.tok
+        n, n_max = 1, max(budgets)
+        while n < n_max:
+            if n % check_every == 0 and self._check(g):
+                break
+            self._advance(shared, rows_family, tag, sample)  # step on token n, sample token n + 1
+            n += 1
+        done = self._check(g)
+        new = g["ring"][:, :n]
+        # what this call leaves in the caches, for a following generate(extend=True).  n - 1 tokens were fed since token 1 was
+        # sampled: counted back from where the rows stand now, a window roll in between is accounted for
+        lengths = [p - (n - 1) for p in self._row_positions()]
+        cache_rows, pending, real = generate_tail_rows(lengths, new.cpu().tolist(), eos_rows, budgets, n, idle=idle)
+        self.tail = {"cache_rows": cache_rows, "pending": pending}
+        # The trim of all-pad columns differs between the two calls, and stays so.
+        if done and mode["per_row"]:
+            # per-row arguments: stop where the longest row ended, by the tail's count of real tokens (0 for an idle row)
+            n = max(1, min(n, max(real)))
+        elif done and eos_rows[0]:
+            # scalars (HF stops at the step where the last row finished): only with EOS ids, and by each row's first EOS hit in the
+            # ring -- an idle row whose pad is no EOS id has none, counts as n and keeps the result untrimmed
+            hit = torch.zeros_like(new, dtype=torch.bool)
+            for e in eos_rows[0]:
+                hit |= new == e
+            first = torch.where(hit.any(1), hit.int().argmax(1), torch.full_like(hit[:, 0], n, dtype=torch.int64))
+            n = min(n, int(first.max()) + 1)
+        return torch.cat([input_ids.long(), new[:, :n].long()], dim=1)  # (rows past their end already hold their own pad)
 
     # ---- speculative decoding --------------------------------------------------------------------------------------------
     def _spec_check_model(self, T):
@@ -513,44 +606,10 @@ class GraphedDecoder:
         ops.sample_launch(logits.view(-1, logits.shape[-1]), st["argmax_params"], st["t"], st["pred"], st["status"], st["ws"],
                           greedy=True)
 
-    @torch.inference_mode()
-    def _capture_spec(self, bound, T, full):
-        st = self._spec[T]
-        for b in self.blocks:
-            b.attn.use_device_positions(self.pos_rows, self.len_rows, per_row=True)
-            b.attn.decode_len_bound = bound
-        caller = torch.cuda.current_stream(self.device)
-        with torch.cuda.stream(self.stream):
-            self.stream.wait_stream(caller)
-            # warm-up outside the capture: the model and the argmax only -- they append T rows at and above the rows' positions,
-            # which the first replay writes again; the integer kernels move the decoder's words and run in replays alone
-            logits = self.lm.verify(st["tok"])
-            if full:
-                self._spec_tail(st, logits)
-            self.stream.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=self.stream):
-                logits = self.lm.verify(st["tok"])
-                if full:
-                    self._spec_tail(st, logits)
-                    ops.spec_accept(st["params"], st["tok"], st["pred"], st["hist"], st["n_hist"], st["cnt"], st["ring"],
-                                    st["finished"], self.pos_rows, self.len_rows, status=st["status"], steps=st["steps"])
-                    ops.ngram_draft(st["params"], st["tok"], st["hist"], st["n_hist"])
-            self.stream.synchronize()
-        caller.wait_stream(self.stream)
-        self._sync_host_state()
-        family = self.spec_graphs if full else self.verify_graphs
-        family[(bound, T)] = (graph, logits)
-        return family[(bound, T)]
-
     def _replay_spec(self, bound, T, full):
-        family = self.spec_graphs if full else self.verify_graphs
-        graph, logits = family.get((bound, T)) or self._capture_spec(bound, T, full)
-        caller = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(caller)
-        with torch.cuda.stream(self.stream):
-            graph.replay()
-        caller.wait_stream(self.stream)
+        graph, logits = self._graph(self.spec_graphs if full else self.verify_graphs, (bound, T), bound, True, False, self._spec_body,
+                                    self._spec[T], full)
+        self._replay(graph)
         return logits
 
     @torch.inference_mode()
@@ -597,12 +656,8 @@ class GraphedDecoder:
                              f"exceed the cache window {self.max_seq_len} (no window roll inside a speculative run)")
         pad = int(pad_token_id) if pad_token_id is not None else (eos[0] if eos else 0)
         params = ops.spec_params(eos_ids=eos, pad=pad, max_new_tokens=max_new_tokens, ngram_max=ngram)
-        logits = self.prefill(input_ids, attention_mask if ragged is not None else None)
-        if ragged is not None:
-            last = torch.tensor([s + n - 1 for s, n in zip(starts, lengths)], dtype=torch.int64, device=self.device)
-            logits = logits[torch.arange(B, device=self.device), last].unsqueeze(1).contiguous()
-        else:
-            self.seek_rows(lengths)  # always per-row: equal positions diverge at the first step
+        # always per-row: equal positions diverge at the first step (unpadded: the shared position is every row's length)
+        logits, _ = self._first_logits(input_ids, attention_mask, per_row=True)
         st = self._spec_state(T, logits.shape[-1], max_new_tokens, max(lengths) + max_new_tokens)
         first = ops.sample_tokens(logits, do_sample=False)  # token 1, eagerly (raises on NaN / +inf logits)
         # reset the decoder-owned words outside any capture: prompt and token 1 into the history, token 1 into the ring
@@ -662,53 +717,13 @@ class GraphedDecoder:
         params = ops.sample_params_rows(B, do_sample=args["do_sample"], temperature=args["temperature"], top_k=args["top_k"],
                                         top_p=args["top_p"], seed=args["seed"], eos_ids=eos_rows, pad=pad_token_id)
         proc_bytes = ops.sample_proc_params_rows(B, args["repetition_penalty"], args["min_new_tokens"])
-        n_max = max(max_rows)
-        idle = []
-        if extend:
-            logits, idle = self._extend_turn(input_ids, attention_mask)
-        else:
-            ragged = self._ragged(input_ids, attention_mask)
-            logits = self.prefill(input_ids, attention_mask if ragged is not None else None)
-            if ragged is not None:  # the first token of row b comes from its column start_b + L_b - 1
-                last = torch.tensor([s + n - 1 for s, n in zip(*ragged)], dtype=torch.int64, device=self.device)
-                logits = logits[torch.arange(B, device=self.device), last].unsqueeze(1).contiguous()
-            else:
-                self.seek_rows([self.position] * B)  # the rows family reads per-row positions
-        g = self._gen_rows_state(logits.shape[-1], n_max)
-        # reset every decoder-owned device word, outside any capture; every row's token index restarts at 1
-        g["params"].copy_(params)
-        g["proc"].copy_(proc_bytes)
-        g["max_new"].copy_(torch.tensor(max_rows, dtype=torch.int32))
-        g["t"].fill_(1)
-        g["ring"].zero_()
-        g["finished"].zero_()
-        if idle:  # nothing to process: the row starts finished and emits pads
-            g["finished"][torch.tensor(idle, device=self.device)] = 1
-        g["status"].zero_()
-        prev = self._history_of_last
-        if not extend or prev is None:
-            g["history"].zero_()  # (extend after a call that kept no history: the sampler knows this turn's ids only)
-        elif prev is not g["history"] and prev.shape == g["history"].shape:
-            g["history"].copy_(prev)  # the ids seen so far move along
-        ops.sample_history(input_ids, g["vocab"], out=g["history"])
-        self._history_of_last = g["history"]
-        self._sample_rows(logits)  # token 1, eagerly, into self.tok
-        n = 1
-        while n < n_max:
-            if n % check_every == 0 and self._check(g):
-                break
-            self.tail = None
-            self._advance_rows(rows_sampler=True)  # step on token n, sample token n + 1
-            n += 1
-        done = self._check(g)
-        new = g["ring"][:, :n]
-        lengths = [p - (n - 1) for p in self._row_positions()]
-        cache_rows, pending, real = generate_tail_rows(lengths, new.cpu().tolist(), eos_rows, max_rows, n, idle=idle)
-        self.tail = {"cache_rows": cache_rows, "pending": pending}
-        if done:  # stop where the longest row ended: drop the all-pad columns after it
-            n = max(1, min(n, max(real)))
-            new = new[:, :n]
-        return torch.cat([input_ids.long(), new.long()], dim=1)  # (rows past their end already hold their own pad)
+        # the rows family reads per-row positions, and its sampler always runs the processors
+        logits, idle = self._first_logits(input_ids, attention_mask, extend, per_row=True)
+        g = self._gen_state(logits.shape[-1], max(max_rows), per_row=True)
+        return self._generate_loop(input_ids, logits, idle, extend, check_every, {
+            "g": g, "words": {"params": params, "proc": proc_bytes, "max_new": torch.tensor(max_rows, dtype=torch.int32)},
+            "sample": lambda lg: self._sample(lg, g, True, False, True), "advance": (None, self.rows_gen_graphs, None),
+            "eos": eos_rows, "budgets": max_rows, "per_row": True, "proc": True, "moved": None})
 
     @torch.inference_mode()
     def generate(self, input_ids, max_new_tokens, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
@@ -779,52 +794,16 @@ class GraphedDecoder:
         proc_bytes = ops.sample_proc_params(repetition_penalty, min_new_tokens)
         proc = float(repetition_penalty) != 1.0 or int(min_new_tokens) > 0
         greedy = not do_sample or float(temperature) <= 0
-        idle = []
-        if extend:
-            logits, idle = self._extend_turn(input_ids, attention_mask)
-        else:
-            ragged = self._ragged(input_ids, attention_mask)
-            logits = self.prefill(input_ids, attention_mask if ragged is not None else None)
-            if ragged is not None:  # the first token of row b comes from its column start_b + L_b - 1
-                last = torch.tensor([s + n - 1 for s, n in zip(*ragged)], dtype=torch.int64, device=self.device)
-                logits = logits[torch.arange(self.batch, device=self.device), last].unsqueeze(1).contiguous()
+        logits, idle = self._first_logits(input_ids, attention_mask, extend)
         before = self._gen
         g = self._gen_state(logits.shape[-1], max_new_tokens)
-        # reset every decoder-owned device word, outside any capture
-        g["params"].copy_(params)
-        g["t"].fill_(1)
-        g["ring"].zero_()
-        g["finished"].zero_()
-        if idle:  # nothing to process: the row starts finished and emits pads
-            g["finished"][torch.tensor(idle, device=self.device)] = 1
-        g["status"].zero_()
-        self._history_of_last = g["history"] if proc else None
-        if proc:
-            g["proc"].copy_(proc_bytes)
-            if not extend:
-                g["history"].zero_()
-            elif before is not None and before is not g and before["vocab"] == g["vocab"]:
-                g["history"].copy_(before["history"])  # the words were reallocated (a longer ring): the ids seen so far move along
-            ops.sample_history(input_ids, g["vocab"], out=g["history"])
-        self._sample(logits, greedy, proc)  # token 1, eagerly, into self.tok
-        n = 1
-        while n < max_new_tokens:
-            if n % check_every == 0 and self._check(g):
-                break
-            self._advance(greedy=greedy, proc=proc)  # step on token n, sample token n + 1
-            n += 1
-        done = self._check(g)
-        new = g["ring"][:, :n]
-        # what this call leaves in the caches, for a following generate(extend=True).  n - 1 tokens were fed since token 1 was
-        # sampled: counted back from where the rows stand now, a window roll in between is accounted for
-        lengths = [p - (n - 1) for p in self._row_positions()]
-        cache_rows, pending = generate_tail(lengths, new.cpu().tolist(), eos, n, idle=idle)
-        self.tail = {"cache_rows": cache_rows, "pending": pending}
-        if done and eos:  # HF stops at the step where the last row finished: drop the all-pad columns after it
-            hit = torch.zeros_like(new, dtype=torch.bool)
-            for e in eos:
-                hit |= new == e
-            first = torch.where(hit.any(1), hit.int().argmax(1), torch.full_like(hit[:, 0], n, dtype=torch.int64))
-            n = min(n, int(first.max()) + 1)
-            new = new[:, :n]
-        return torch.cat([input_ids.long(), new.long()], dim=1)
+        moved = before["history"] if before is not None and before is not g and before["vocab"] == g["vocab"] else None
+        # Graphs and sampler kernels: without the processors the sampler is launched without proc / history (the kernels that
+        # read neither) and captured into gen_graphs / row_gen_graphs; attaching them always would give the same tokens at
+        # repetition_penalty = 1, slower.  greedy: one pass only, in graphs of its own key.
+        return self._generate_loop(input_ids, logits, idle, extend, check_every, {
+            "g": g, "words": {"params": params, "proc": proc_bytes} if proc else {"params": params},
+            "sample": lambda lg: self._sample(lg, g, False, greedy, proc),
+            "advance": (self.proc_gen_graphs, self.row_proc_gen_graphs, greedy) if proc else (self.gen_graphs, self.row_gen_graphs, greedy),
+            "eos": [eos] * self.batch, "budgets": [max_new_tokens] * self.batch, "per_row": False, "proc": proc,
+            "moved": moved})

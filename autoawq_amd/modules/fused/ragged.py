@@ -69,20 +69,9 @@ def generate_tail(lengths, ring, eos, n, idle=()):
     that feeds token i, so ring[b][:n - 1] were fed (appended to the cache, real tokens and pads alike) and ring[b][n - 1] was not.
       cache_rows[b] = lengths[b] + the real tokens that were fed: the rows above hold pads and are dead;
       pending[b]    = the last real token if it was not fed (the row never finished, or finished on token n), else None.
-    Pure host code: lists or a CPU tensor in, two lists out."""
-    eos = set(int(e) for e in eos)
-    cache_rows, pending = [], []
-    for b, L in enumerate(lengths):
-        row = [int(t) for t in ring[b][:n]]
-        if len(row) != n or n < 1:
-            raise ValueError(f"generate_tail: row {b} of the ring holds {len(row)} tokens, n = {n}")
-        if b in idle:
-            real = 0
-        else:
-            real = next((i + 1 for i, t in enumerate(row) if t in eos), n)
-        cache_rows.append(int(L) + min(real, n - 1))
-        pending.append(row[n - 1] if real == n else None)
-    return cache_rows, pending
+    Pure host code: lists or a CPU tensor in, two lists out (a ring that holds fewer than n tokens, or n < 1: ValueError)."""
+    B = len(lengths)  # (the uniform case of generate_tail_rows: every row the same EOS ids and the budget n)
+    return _tail_rows("generate_tail", lengths, ring, [eos] * B, [n] * B, n, idle)[:2]
 
 
 def generate_tail_rows(lengths, ring, eos_rows, max_rows, n, idle=()):
@@ -91,11 +80,16 @@ def generate_tail_rows(lengths, ring, eos_rows, max_rows, n, idle=()):
     real[b]: the row's real tokens -- up to and including its first EOS id, at most max_rows[b].  A row that used up a budget
     below n has fed its last token to a decode step; it is still handed back as pending with the cache row under it dead, which is
     where a call with that budget for every row leaves it (the token is then fed again by the next turn's extend)."""
+    return _tail_rows("generate_tail_rows", lengths, ring, eos_rows, max_rows, n, idle)
+
+
+def _tail_rows(fn, lengths, ring, eos_rows, max_rows, n, idle):
+    """generate_tail_rows' body; fn: the public function named in the refusal"""
     cache_rows, pending, reals = [], [], []
     for b, L in enumerate(lengths):
         row = [int(t) for t in ring[b][:n]]
         if len(row) != n or n < 1:
-            raise ValueError(f"generate_tail_rows: row {b} of the ring holds {len(row)} tokens, n = {n}")
+            raise ValueError(f"{fn}: row {b} of the ring holds {len(row)} tokens, n = {n}")
         eos = set(int(e) for e in eos_rows[b])
         m = min(int(max_rows[b]), n)
         if b in idle:

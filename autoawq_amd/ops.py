@@ -1158,30 +1158,31 @@ def _logits_rows(logits):
     return rows, rows.stride(0)
 
 
-def sample_launch(logits, params, t, out, status, workspace, ring=None, finished=None, greedy=False, proc=None, history=None):
-    """The raw launch (no validation of the configuration, no sync): every buffer a device tensor the caller owns --
-    params (64 bytes, sample_params), t (int32 [1]), out (int64, one element per row, any row stride), status (int32,
-    ceil(B / 32) words), workspace (zeroed once), ring (int32 [B, cap]) and finished (int32 [B]) optional.  proc (16 bytes,
-    sample_proc_params) with history (int32 [B, >= ceil(V / 32)], sample_history): the logit processors, and the emitted
-    tokens ORed into the history (awq_sample_tokens_ex).  Capturable."""
+def _sample_launch_args(fn, a, logits, params, t, out, status, workspace, ring, finished, greedy, proc, history, max_new=None,
+                        per_row=False):
+    """What sample_launch and sample_launch_rows share: the checks of the buffers both forms take, in the order they always
+    had (messages prefixed with `fn`; per_row: params and proc hold one struct per row), and the fields their argument structs
+    have in common.  Returns (the logits' rows, B)."""
     rows, rs = _logits_rows(logits)
     B, V = rows.shape
-    _require_gpu(rows, params, t, out, status, workspace, ring, finished, proc, history)
+    _require_gpu(rows, params, t, out, status, workspace, ring, finished, proc, history, max_new)
     if (proc is None) != (history is None):
-        raise _lib.AwqHipError("sample_launch: proc and history go together")
+        raise _lib.AwqHipError(f"{fn}: proc and history go together")
     if history is not None and (history.dtype != torch.int32 or history.dim() != 2 or history.shape[0] != B
                                 or history.shape[1] < sample_history_words(V) or history.stride(1) != 1):
-        raise _lib.AwqHipError(f"sample_launch: history must be int32 [{B}, >= {sample_history_words(V)}] with unit column stride")
-    if proc is not None and (proc.numel() * proc.element_size() < ctypes.sizeof(_lib.AwqSampleProc)):
-        raise _lib.AwqHipError("sample_launch: proc must hold 16 bytes (sample_proc_params)")
+        raise _lib.AwqHipError(f"{fn}: history must be int32 [{B}, >= {sample_history_words(V)}] with unit column stride")
+    if per_row:
+        if not params.is_contiguous() or params.numel() * params.element_size() < B * ctypes.sizeof(_lib.AwqSampleParams):
+            raise _lib.AwqHipError(f"{fn}: params must hold {B} x 64 contiguous bytes (sample_params_rows)")
+        if proc is not None and (not proc.is_contiguous() or proc.numel() * proc.element_size() < B * ctypes.sizeof(_lib.AwqSampleProc)):
+            raise _lib.AwqHipError(f"{fn}: proc must hold {B} x 16 contiguous bytes (sample_proc_params_rows)")
+    elif proc is not None and (proc.numel() * proc.element_size() < ctypes.sizeof(_lib.AwqSampleProc)):
+        raise _lib.AwqHipError(f"{fn}: proc must hold 16 bytes (sample_proc_params)")
     if out.numel() < B or status.numel() * 32 < B or (finished is not None and finished.numel() < B):
-        raise _lib.AwqHipError("sample_launch: out / status / finished too small for the batch")
+        raise _lib.AwqHipError(f"{fn}: out / status / finished too small for the batch")
     if ring is not None and (ring.dim() != 2 or ring.shape[0] != B or not ring.is_contiguous() or ring.dtype != torch.int32):
-        raise _lib.AwqHipError("sample_launch: ring must be a contiguous int32 [B, cap] tensor")
-    if out.dtype != torch.int64 or t.dtype != torch.int32 or (finished is not None and finished.dtype != torch.int32):
-        raise _lib.AwqHipError("sample_launch: out int64, t and finished int32 expected")
-    a = _lib.AwqSampleArgs()
-    a.struct_bytes = ctypes.sizeof(_lib.AwqSampleArgs)
+        raise _lib.AwqHipError(f"{fn}: ring must be a contiguous int32 [B, cap] tensor")
+    a.struct_bytes = ctypes.sizeof(a)
     a.flags = SAMPLE_FLAG_GREEDY if greedy else 0
     a.logits, a.B, a.V, a.row_stride = _ptr(rows), B, V, rs
     a.params, a.t = _ptr(params), _ptr(t)
@@ -1189,6 +1190,20 @@ def sample_launch(logits, params, t, out, status, workspace, ring=None, finished
     a.ring, a.ring_cap = _ptr(ring), ring.shape[1] if ring is not None else 0
     a.finished, a.status = _ptr(finished), _ptr(status)
     a.workspace, a.workspace_bytes = _ptr(workspace), workspace.numel()
+    return rows, B
+
+
+def sample_launch(logits, params, t, out, status, workspace, ring=None, finished=None, greedy=False, proc=None, history=None):
+    """The raw launch (no validation of the configuration, no sync): every buffer a device tensor the caller owns --
+    params (64 bytes, sample_params), t (int32 [1]), out (int64, one element per row, any row stride), status (int32,
+    ceil(B / 32) words), workspace (zeroed once), ring (int32 [B, cap]) and finished (int32 [B]) optional.  proc (16 bytes,
+    sample_proc_params) with history (int32 [B, >= ceil(V / 32)], sample_history): the logit processors, and the emitted
+    tokens ORed into the history (awq_sample_tokens_ex).  Capturable."""
+    a = _lib.AwqSampleArgs()
+    rows, B = _sample_launch_args("sample_launch", a, logits, params, t, out, status, workspace, ring, finished, greedy, proc,
+                                  history)
+    if out.dtype != torch.int64 or t.dtype != torch.int32 or (finished is not None and finished.dtype != torch.int32):
+        raise _lib.AwqHipError("sample_launch: out int64, t and finished int32 expected")
     with torch.cuda.device(rows.device):
         a.stream = _stream()
         if proc is None:
@@ -1200,6 +1215,41 @@ def sample_launch(logits, params, t, out, status, workspace, ring=None, finished
             q.proc, q.history, q.history_stride = _ptr(proc), _ptr(history), history.stride(0)
             rc = _lib.lib().awq_sample_tokens_ex(ctypes.byref(a), ctypes.byref(q))
     _lib.check(rc, "awq_sample_tokens" if proc is None else "awq_sample_tokens_ex")
+    return out
+
+
+def _sample_tokens(fn, launch, logits, params, proc, use_proc, t, greedy, out, ring, finished, status, history, max_new=None):
+    """What sample_tokens and sample_tokens_rows share once the configuration is checked and packed (params, proc: CPU bytes; t: a
+    device tensor or a list of ints; max_new: the rows form's list of budgets): the parameters to the device, out / status /
+    workspace / history, the launch and, with a status of its own, the bad-row report."""
+    rows, _ = _logits_rows(logits)
+    _require_gpu(rows)
+    B, V = rows.shape
+    dev = rows.device
+    need = sample_workspace_bytes(B, V)
+    if need == 0:
+        err = _lib.AwqHipError(f"{fn}: no kernel for B = {B}, V = {V} (limits B <= 1024, V <= 2^20)")
+        err.code = _lib.ERR_UNSUPPORTED
+        raise err
+    with torch.cuda.device(dev):
+        params_d = params.to(dev, non_blocking=False)
+        t_d = t if isinstance(t, torch.Tensor) else torch.tensor(t, dtype=torch.int32, device=dev)
+        if out is None:
+            out = torch.empty(B, dtype=torch.int64, device=dev)
+        own_status = status is None
+        if own_status:
+            status = torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev)
+        ws = _sample_workspace(dev, need)
+        proc_d = hist = None
+        if use_proc:
+            proc_d = proc.to(dev, non_blocking=False)
+            hist = history if history is not None else torch.zeros((B, sample_history_words(V)), dtype=torch.int32, device=dev)
+        more = {} if max_new is None else {"max_new": torch.tensor(max_new, dtype=torch.int32, device=dev)}
+        launch(rows, params_d, t_d, out, status, ws, ring=ring, finished=finished, greedy=greedy, proc=proc_d, history=hist, **more)
+        if own_status:
+            bad = [r for r in range(B) if (int(status[r // 32].item()) >> (r % 32)) & 1] if bool(status.any()) else []
+            if bad:
+                raise _lib.AwqHipError(f"{fn}: rows {bad} hold NaN / +inf logits or keep no token (emitted pad)")
     return out
 
 
@@ -1224,35 +1274,8 @@ def sample_tokens(logits, *, do_sample, temperature=1.0, top_k=0, top_p=1.0, see
                            pad=pad)
     if not isinstance(t, torch.Tensor) and int(t) < 1:
         raise ValueError(f"t is the 1-based token index, got {t}")
-    rows, _ = _logits_rows(logits)
-    _require_gpu(rows)
-    B, V = rows.shape
-    dev = rows.device
-    need = sample_workspace_bytes(B, V)
-    if need == 0:
-        err = _lib.AwqHipError(f"sample_tokens: no kernel for B = {B}, V = {V} (limits B <= 1024, V <= 2^20)")
-        err.code = _lib.ERR_UNSUPPORTED
-        raise err
-    with torch.cuda.device(dev):
-        params_d = params.to(dev, non_blocking=False)
-        t_d = t if isinstance(t, torch.Tensor) else torch.tensor([int(t)], dtype=torch.int32, device=dev)
-        if out is None:
-            out = torch.empty(B, dtype=torch.int64, device=dev)
-        own_status = status is None
-        if own_status:
-            status = torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev)
-        ws = _sample_workspace(dev, need)
-        proc_d = hist = None
-        if use_proc:
-            proc_d = proc.to(dev, non_blocking=False)
-            hist = history if history is not None else torch.zeros((B, sample_history_words(V)), dtype=torch.int32, device=dev)
-        sample_launch(rows, params_d, t_d, out, status, ws, ring=ring, finished=finished, greedy=not do_sample or temperature <= 0,
-                      proc=proc_d, history=hist)
-        if own_status:
-            bad = [r for r in range(B) if (int(status[r // 32].item()) >> (r % 32)) & 1] if bool(status.any()) else []
-            if bad:
-                raise _lib.AwqHipError(f"sample_tokens: rows {bad} hold NaN / +inf logits or keep no token (emitted pad)")
-    return out
+    return _sample_tokens("sample_tokens", sample_launch, logits, params, proc, use_proc, t if isinstance(t, torch.Tensor) else [int(t)],
+                          not do_sample or temperature <= 0, out, ring, finished, status, history)
 
 
 # ---- the sampler's rows form: per-row parameters and token indices (awq_sample_tokens_rows) ------------------------------------
@@ -1329,22 +1352,9 @@ def sample_launch_rows(logits, params, t, out, status, workspace, ring=None, fin
     history as in sample_launch; max_new (int32 [B], with finished): row r latches finished[r] in the launch that emits its
     token index max_new[r] (<= 0: no limit).  greedy: argmax for every row in one launch.  No validation of the configuration,
     no sync.  Capturable."""
-    rows, rs = _logits_rows(logits)
-    B, V = rows.shape
-    _require_gpu(rows, params, t, out, status, workspace, ring, finished, proc, history, max_new)
-    if (proc is None) != (history is None):
-        raise _lib.AwqHipError("sample_launch_rows: proc and history go together")
-    if history is not None and (history.dtype != torch.int32 or history.dim() != 2 or history.shape[0] != B
-                                or history.shape[1] < sample_history_words(V) or history.stride(1) != 1):
-        raise _lib.AwqHipError(f"sample_launch_rows: history must be int32 [{B}, >= {sample_history_words(V)}] with unit column stride")
-    if not params.is_contiguous() or params.numel() * params.element_size() < B * ctypes.sizeof(_lib.AwqSampleParams):
-        raise _lib.AwqHipError(f"sample_launch_rows: params must hold {B} x 64 contiguous bytes (sample_params_rows)")
-    if proc is not None and (not proc.is_contiguous() or proc.numel() * proc.element_size() < B * ctypes.sizeof(_lib.AwqSampleProc)):
-        raise _lib.AwqHipError(f"sample_launch_rows: proc must hold {B} x 16 contiguous bytes (sample_proc_params_rows)")
-    if out.numel() < B or status.numel() * 32 < B or (finished is not None and finished.numel() < B):
-        raise _lib.AwqHipError("sample_launch_rows: out / status / finished too small for the batch")
-    if ring is not None and (ring.dim() != 2 or ring.shape[0] != B or not ring.is_contiguous() or ring.dtype != torch.int32):
-        raise _lib.AwqHipError("sample_launch_rows: ring must be a contiguous int32 [B, cap] tensor")
+    a = _lib.AwqSampleRowsArgs()
+    rows, B = _sample_launch_args("sample_launch_rows", a, logits, params, t, out, status, workspace, ring, finished, greedy, proc,
+                                  history, max_new, per_row=True)
     if out.dtype != torch.int64 or (finished is not None and finished.dtype != torch.int32):
         raise _lib.AwqHipError("sample_launch_rows: out int64 and finished int32 expected")
     for name, w in (("t", t), ("max_new", max_new)):
@@ -1352,15 +1362,6 @@ def sample_launch_rows(logits, params, t, out, status, workspace, ring=None, fin
             raise _lib.AwqHipError(f"sample_launch_rows: {name} must be a contiguous int32 [{B}] tensor")
     if max_new is not None and finished is None:
         raise _lib.AwqHipError("sample_launch_rows: max_new latches `finished`: pass both")
-    a = _lib.AwqSampleRowsArgs()
-    a.struct_bytes = ctypes.sizeof(_lib.AwqSampleRowsArgs)
-    a.flags = SAMPLE_FLAG_GREEDY if greedy else 0
-    a.logits, a.B, a.V, a.row_stride = _ptr(rows), B, V, rs
-    a.params, a.t = _ptr(params), _ptr(t)
-    a.out, a.out_stride = _ptr(out), out.stride(0) if out.dim() else 1
-    a.ring, a.ring_cap = _ptr(ring), ring.shape[1] if ring is not None else 0
-    a.finished, a.status = _ptr(finished), _ptr(status)
-    a.workspace, a.workspace_bytes = _ptr(workspace), workspace.numel()
     a.proc, a.history, a.history_stride = _ptr(proc), _ptr(history), history.stride(0) if history is not None else 0
     a.max_new = _ptr(max_new)
     with torch.cuda.device(rows.device):
@@ -1391,8 +1392,8 @@ def sample_tokens_rows(logits, *, do_sample, temperature=1.0, top_k=0, top_p=1.0
         raise ValueError("sample_tokens_rows: repetition_penalty needs a history of the ids seen (sample_history)")
     use_proc = history is not None or any(int(m) > 0 for m in mins)
     if not isinstance(t, torch.Tensor):
-        t_rows = [int(v) for v in per_row("t", t, B)]
-        for r, v in enumerate(t_rows):
+        t = [int(v) for v in per_row("t", t, B)]
+        for r, v in enumerate(t):
             if v < 1:
                 raise ValueError(f"row {r}: t is the 1-based token index, got {v}")
     max_rows = None
@@ -1402,35 +1403,8 @@ def sample_tokens_rows(logits, *, do_sample, temperature=1.0, top_k=0, top_p=1.0
             raise ValueError("sample_tokens_rows: max_new_tokens latches `finished`: pass a finished tensor")
     ds, temps = per_row("do_sample", do_sample, B), per_row("temperature", temperature, B)
     greedy = all(not d or float(T) <= 0 for d, T in zip(ds, temps))
-    _require_gpu(rows)
-    dev = rows.device
-    need = sample_workspace_bytes(B, V)
-    if need == 0:
-        err = _lib.AwqHipError(f"sample_tokens_rows: no kernel for B = {B}, V = {V} (limits B <= 1024, V <= 2^20)")
-        err.code = _lib.ERR_UNSUPPORTED
-        raise err
-    with torch.cuda.device(dev):
-        params_d = params.to(dev, non_blocking=False)
-        t_d = t if isinstance(t, torch.Tensor) else torch.tensor(t_rows, dtype=torch.int32, device=dev)
-        if out is None:
-            out = torch.empty(B, dtype=torch.int64, device=dev)
-        own_status = status is None
-        if own_status:
-            status = torch.zeros((B + 31) // 32, dtype=torch.int32, device=dev)
-        ws = _sample_workspace(dev, need)
-        proc_d = hist = max_d = None
-        if use_proc:
-            proc_d = proc.to(dev, non_blocking=False)
-            hist = history if history is not None else torch.zeros((B, sample_history_words(V)), dtype=torch.int32, device=dev)
-        if max_rows is not None:
-            max_d = torch.tensor(max_rows, dtype=torch.int32, device=dev)
-        sample_launch_rows(rows, params_d, t_d, out, status, ws, ring=ring, finished=finished, greedy=greedy, proc=proc_d,
-                           history=hist, max_new=max_d)
-        if own_status:
-            bad = [r for r in range(B) if (int(status[r // 32].item()) >> (r % 32)) & 1] if bool(status.any()) else []
-            if bad:
-                raise _lib.AwqHipError(f"sample_tokens_rows: rows {bad} hold NaN / +inf logits or keep no token (emitted pad)")
-    return out
+    return _sample_tokens("sample_tokens_rows", sample_launch_rows, rows, params, proc, use_proc, t, greedy, out, ring, finished, status,
+                          history, max_new=max_rows)
 
 
 # ---- speculative decoding: the verify step's attention (csrc/verify_attn.hip), acceptance and prompt-lookup drafts (csrc/spec.hip)

@@ -86,3 +86,48 @@ def test_abi_table_has_the_per_row_entry_points(name, shared, rows_arg):
     want = [a.replace("pos_dev", rows_arg).replace("len_dev", rows_arg) for a in _header_args(shared)
             if a.split()[-1].lstrip("*") not in drop]
     assert args == want
+
+
+def _tail_restated(lengths, ring, eos, n, idle):
+    """generate_tail's docstring, restated on its own: real = the row's tokens up to and including its first EOS id (n without
+    one, 0 for an idle row); the cache holds the prompt and the real tokens that were fed (n - 1 were fed at the most); the last
+    real token is pending iff it is token n"""
+    cache_rows, pending = [], []
+    for b, L in enumerate(lengths):
+        row = list(ring[b][:n])
+        hits = [i for i, t in enumerate(row) if t in eos]
+        real = 0 if b in idle else hits[0] + 1 if hits else n
+        cache_rows.append(L + min(real, n - 1))
+        pending.append(row[n - 1] if real == n else None)
+    return cache_rows, pending
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_generate_tail_is_the_uniform_case_of_generate_tail_rows(seed):
+    """generate_tail(lengths, ring, eos, n, idle) is generate_tail_rows with every row's EOS ids = eos and every budget = n, without
+    its third result, and both are the restatement above: a seeded sweep over batch sizes, n = 1 included, rings longer than n,
+    idle rows, no / one / several EOS ids."""
+    import random
+
+    from autoawq_amd.modules.fused.ragged import generate_tail, generate_tail_rows
+
+    rng = random.Random(seed)
+    idle_seen = single = 0
+    for _ in range(400):
+        B = rng.randint(1, 5)
+        n = 1 if rng.random() < 0.2 else rng.randint(2, 9)
+        eos = rng.sample(range(6), rng.randint(0, 3))          # a small alphabet: EOS ids hit often, at every column
+        ring = [[rng.randrange(6) for _ in range(n + rng.randint(0, 3))] for _ in range(B)]
+        lengths = [rng.randint(0, 40) for _ in range(B)]
+        idle = [b for b in range(B) if rng.random() < 0.25]
+        idle_seen += bool(idle)
+        single += n == 1
+        want = _tail_restated(lengths, ring, eos, n, idle)
+        assert generate_tail_rows(lengths, ring, [eos] * B, [n] * B, n, idle)[:2] == want
+        assert generate_tail(lengths, ring, eos, n, idle) == want
+        assert generate_tail(lengths, torch.tensor([r[:n] for r in ring]), eos, n, idle=idle) == want
+    assert idle_seen > 100 and single > 30
+    with pytest.raises(ValueError, match="^generate_tail: row 0"):
+        generate_tail([7], [[1, 2]], [], 3)
+    with pytest.raises(ValueError, match="^generate_tail_rows: row 0"):
+        generate_tail_rows([7], [[1, 2]], [[]], [3], 3)
