@@ -79,6 +79,12 @@ class AwqSpecArgs(ctypes.Structure):
                 ("len_rows", c_void_p), ("status", c_void_p), ("steps", c_void_p), ("stream", c_void_p)]
 
 
+class AwqLogprobArgs(ctypes.Structure):
+    """struct AwqLogprobArgs of include/awq_hip.h (same field order)."""
+    _fields_ = [("logits", c_void_p), ("logits_stride", c_int64), ("ids", c_void_p), ("ids_stride", c_int64), ("out", c_void_p),
+                ("out_stride", c_int64), ("slot", c_void_p), ("out_cap", c_int64), ("R", c_int64), ("V", c_int64), ("stream", c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol include/awq_hip.h declares
 # (tests/test_boundary.py cross-checks this table against the header and the .so).
 SIGNATURES = {
@@ -166,6 +172,7 @@ SIGNATURES = {
     "awq_prefill_attention_rows": (c_int, [c_void_p] * 6 + [c_int64] * 7 + [c_float, c_float, c_void_p, c_void_p]),
     "awq_spec_accept": (c_int, [ctypes.POINTER(AwqSpecArgs)]),
     "awq_ngram_draft": (c_int, [ctypes.POINTER(AwqSpecArgs)]),
+    "awq_token_logprobs": (c_int, [ctypes.POINTER(AwqLogprobArgs)]),
 }
 
 

@@ -254,3 +254,6 @@ int awq_verify_attention_splits_impl(int max_len, int B, int T, int Hq, int Hkv)
 size_t awq_verify_attention_workspace_bytes_impl(int B, int T, int Hq, int splits);
 // (a: an fp16 cache, the per-row word and max_len; seq_len, softcap, alibi and the tables are not read)
 int awq_launch_verify_attention(const AwqAttnArgs& a, int T);
+
+// logprob.hip: log-probability of one id per row of fp16 logits, one block per row (capi.hip checks the arguments)
+int awq_launch_token_logprobs(const AwqLogprobArgs& a);

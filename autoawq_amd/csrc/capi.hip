@@ -961,3 +961,12 @@ int awq_kv_dequant_fp8(const uint8_t* cache, const float* scales, uint16_t* out,
     return awq_launch_kv_dequant_fp8(cache, scales, out, (int)B, (int)n, (int)n_kv_heads, (int)max_seq,
                                      static_cast<hipStream_t>(stream));
 }
+
+// ---- token log-probabilities (logprob.hip): every refusal before the launch
+int awq_token_logprobs(const AwqLogprobArgs* a) {
+    if (!a) return AWQ_ERR_NULL;
+    if (a->V < 1 || a->V > ((int64_t)1 << 20) || a->R < 0 || a->R > INT32_MAX || a->logits_stride < a->V) return AWQ_ERR_BAD_SHAPE;
+    if (a->R == 0) return AWQ_OK;
+    if (!a->logits || !a->ids || !a->out) return AWQ_ERR_NULL;
+    return awq_launch_token_logprobs(*a);
+}

@@ -37,11 +37,14 @@ behind the scalar call and the call with per-row arguments.  The families, what 
                                             spec_graphs[(bound, T)]        generate(draft_tokens=T - 1)      verify step + argmax +
                                                                                                              accept + draft
                                             verify_graphs[(bound, T)]      verify                            verify step
+    lp_gen_graphs[(bound, (greedy, proc))]  row_lp_gen_graphs[...]         generate(logprobs=True)           step + sampler + log-prob
+                                            row_lp_gen_graphs[(bound,      ... with per-row arguments        step + rows sampler +
+                                                               "rows")]                                      log-prob
     (left: one shared position, the words `pos` / `len`; right: per-row positions, `pos_rows` / `len_rows`)
 
 The graphs bake in the addresses of the device words their sampler reads, so a family lives as long as its words: `_gen_state`
 drops the four scalar generation families when it reallocates (a longer ring, another vocabulary), its per-row form drops
-`rows_gen_graphs`, `_spec_state(T)` the speculative graphs of that T.
+`rows_gen_graphs`, `_spec_state(T)` the speculative graphs of that T; the log-prob graphs go with the state whose sampler they hold.
 
 Token generation (`generate`): the same step, then the sampler (csrc/sample.hip) writing the next ids straight into the step's
 input buffer, a ring of generated tokens and the per-row finished flags.  The host only picks buckets, rolls the window and looks
@@ -83,6 +86,17 @@ modules/fused/ragged.py, generate_tail_rows), and a following `generate(extend=T
 
     out1 = dec.generate(turn1, max_new_tokens=64, eos_token_id=eos)
     out2 = dec.generate(turn2, max_new_tokens=64, eos_token_id=eos, extend=True)   # turn 1 is not prefilled again
+
+Log-probabilities (`generate(logprobs=True)`, `score`): csrc/logprob.hip, one block per row, under the model's own distribution
+(no temperature, top-k / top-p or logit processor).  In `generate` the launch is recorded right behind the sampler: it reads the
+step's logits and the ids the sampler has just written into `tok`, and appends to a ring of its own (`lp` [B, cap] fp32 at the
+per-row slot word `lp_slot`) beside the sampler's words -- no host round trip per token.  Such graphs live in families of their
+own; a call without `logprobs` finds, captures and replays exactly the graphs it did before, and allocates none of this.
+`score` is one prefill and one launch over the [B, S, V] logits with shifted labels.
+
+    out = dec.generate(ids, max_new_tokens=64, logprobs=True)
+    dec.last_logprobs                      # fp32 [batch, n]: aligned with out[:, prompt:], 0.0 past a row's real tokens
+    lp = dec.score(ids, attention_mask)    # fp32 [batch, S]: log p(ids[b, s] | the row's real tokens before it)
 """
 import torch
 
@@ -140,6 +154,9 @@ class GraphedDecoder:
         self._spec = {}          # T -> the device words of the speculative path (allocated by its first use)
         self._verify_T = None    # tokens appended by the last `verify`, until `advance_rows`
         self.last_spec = None
+        self.lp_gen_graphs = {}      # generate(logprobs=True): (bucket bound, (greedy, proc)) -> (graph, logits): step + sampler + log-prob
+        self.row_lp_gen_graphs = {}  # ... at per-row positions; (bucket bound, "rows"): the call with per-row arguments
+        self.last_logprobs = None    # fp32 [batch, n] of the last generate(logprobs=True); None after a call without
         self.tail = None         # what the last plain `generate` left per row: {"cache_rows": [...], "pending": [...]} (generate_tail)
         self.position = 0
         self.positions = None  # per-row mode: the host's position of every row (None: one shared position)
@@ -445,14 +462,23 @@ class GraphedDecoder:
         return self._advance(self.graphs, self.row_graphs)
 
     # ---- generation: sampler in the graph ---------------------------------------------------------------------------------
-    def _gen_state(self, vocab, cap, per_row=False):
+    def _gen_state(self, vocab, cap, per_row=False, logprobs=False):
         """The device words generate owns (per_row: of generate with per-row arguments -- params / proc / t hold one element per
         row, and max_new).  Their addresses are baked into the generation graphs: reallocated (and those graphs dropped) only when
-        the vocabulary or the ring capacity has to grow.  history: the ids seen per row (bit v % 32 of word v / 32), proc: struct
+        the vocabulary or the ring capacity has to grow.  logprobs: also lp (fp32 [B, ring capacity]: the log-probabilities of the
+        generated tokens) and lp_slot (int32 [B]: the column each row writes next) -- added on the first call that asks for them,
+        so the words and graphs of plain calls are untouched, and reallocated with the ring.  history: the ids seen per row (bit v % 32 of word v / 32), proc: struct
         AwqSampleProc -- the logit processors' state."""
         g = self._gen_rows if per_row else self._gen
-        if g is not None and g["vocab"] == vocab and g["ring"].shape[1] >= cap:
-            return g
+        if g is None or g["vocab"] != vocab or g["ring"].shape[1] < cap:
+            g = self._gen_alloc(vocab, cap, per_row)
+        if logprobs and "lp" not in g:
+            with torch.inference_mode(False):
+                g["lp"] = torch.zeros((self.batch, g["ring"].shape[1]), dtype=torch.float32, device=self.device)
+                g["lp_slot"] = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
+        return g
+
+    def _gen_alloc(self, vocab, cap, per_row):
         with torch.inference_mode(False):
             dev, B = self.device, self.batch
             one = (B,) if per_row else ()  # one parameter word per row, or one for all
@@ -469,8 +495,11 @@ class GraphedDecoder:
                 g["max_new"] = torch.zeros(B, dtype=torch.int32, device=dev)
         if per_row:
             self.rows_gen_graphs = {}
+            self.row_lp_gen_graphs = {k: v for k, v in self.row_lp_gen_graphs.items() if k[1] != "rows"}
             self._gen_rows = g
         else:
+            self.lp_gen_graphs = {}
+            self.row_lp_gen_graphs = {k: v for k, v in self.row_lp_gen_graphs.items() if k[1] == "rows"}
             self.gen_graphs = {}
             self.row_gen_graphs = {}
             self.proc_gen_graphs = {}
@@ -484,6 +513,10 @@ class GraphedDecoder:
         launch(logits, g["params"], g["t"], self.tok.view(-1), g["status"], g["ws"], ring=g["ring"], finished=g["finished"],
                greedy=greedy, proc=g["proc"] if proc else None, history=g["history"] if proc else None, **more)
 
+    def _logprob(self, logits, g):
+        """the log-probability of the ids the sampler has just written into the step's input buffer, appended to g's ring"""
+        ops.token_logprobs_launch(logits, self.tok, g["lp"], slot=g["lp_slot"])
+
     def _check(self, g):
         st = g["status"].cpu()
         if bool(st.any()):
@@ -496,7 +529,8 @@ class GraphedDecoder:
         (name -> the CPU bytes this call puts into them), sample (the sampler call: eagerly for token 1, recorded behind the
         step), advance (`_advance`'s two families -- taken after `_gen_state`, which may replace them -- and its tag), eos /
         budgets (one list of EOS ids and one max_new_tokens per row), and per_row / proc / moved for the three places where the
-        scalar call and the call with per-row arguments differ."""
+        scalar call and the call with per-row arguments differ.  logprobs: g holds lp / lp_slot and `sample` ends with the
+        log-prob launch; `last_logprobs` is set from them."""
         g, sample, eos_rows, budgets = mode["g"], mode["sample"], mode["eos"], mode["budgets"]
         shared, rows_family, tag = mode["advance"]
         # reset every decoder-owned device word, outside any capture; every token index restarts at 1
@@ -508,6 +542,9 @@ class GraphedDecoder:
         if idle:  # nothing to process: the row starts finished and emits pads
             g["finished"][torch.tensor(idle, device=self.device)] = 1
         g["status"].zero_()
+        if mode["logprobs"]:
+            g["lp"].zero_()
+            g["lp_slot"].zero_()
         # History carry-over under extend differs between the two calls, and stays so.
         if mode["per_row"]:
             # per-row arguments: the processors always run, and what moves along is the history the LAST generate kept up to
@@ -543,6 +580,10 @@ class GraphedDecoder:
         lengths = [p - (n - 1) for p in self._row_positions()]
         cache_rows, pending, real = generate_tail_rows(lengths, new.cpu().tolist(), eos_rows, budgets, n, idle=idle)
         self.tail = {"cache_rows": cache_rows, "pending": pending}
+        lp = None
+        if mode["logprobs"]:  # a row's slots past its real tokens (the pads after its end, every slot of an idle row) hold 0.0
+            keep = torch.arange(n, device=self.device).view(1, -1) < torch.tensor(real, device=self.device).view(-1, 1)
+            lp = torch.where(keep, g["lp"][:, :n], torch.zeros((), dtype=torch.float32, device=self.device))
         # The trim of all-pad columns differs between the two calls, and stays so.
         if done and mode["per_row"]:
             # per-row arguments: stop where the longest row ended, by the tail's count of real tokens (0 for an idle row)
@@ -555,6 +596,7 @@ class GraphedDecoder:
                 hit |= new == e
             first = torch.where(hit.any(1), hit.int().argmax(1), torch.full_like(hit[:, 0], n, dtype=torch.int64))
             n = min(n, int(first.max()) + 1)
+        self.last_logprobs = None if lp is None else lp[:, :n].contiguous()
         return torch.cat([input_ids.long(), new[:, :n].long()], dim=1)  # (rows past their end already hold their own pad)
 
     # ---- speculative decoding --------------------------------------------------------------------------------------------
@@ -702,7 +744,7 @@ class GraphedDecoder:
         new = torch.where(keep, new, torch.full_like(new, pad))
         return torch.cat([input_ids.long(), new], dim=1)
 
-    def _generate_rows(self, input_ids, args, eos_token_id, pad_token_id, check_every, attention_mask, extend):
+    def _generate_rows(self, input_ids, args, eos_token_id, pad_token_id, check_every, attention_mask, extend, logprobs=False):
         """generate with per-row arguments (see `generate`): every check of the arguments comes before the first launch."""
         B = self.batch
         max_rows = []
@@ -719,16 +761,21 @@ class GraphedDecoder:
         proc_bytes = ops.sample_proc_params_rows(B, args["repetition_penalty"], args["min_new_tokens"])
         # the rows family reads per-row positions, and its sampler always runs the processors
         logits, idle = self._first_logits(input_ids, attention_mask, extend, per_row=True)
-        g = self._gen_state(logits.shape[-1], max(max_rows), per_row=True)
+        g = self._gen_state(logits.shape[-1], max(max_rows), per_row=True, logprobs=logprobs)
+
+        def sample(lg):
+            self._sample(lg, g, True, False, True)
+            if logprobs:
+                self._logprob(lg, g)
         return self._generate_loop(input_ids, logits, idle, extend, check_every, {
             "g": g, "words": {"params": params, "proc": proc_bytes, "max_new": torch.tensor(max_rows, dtype=torch.int32)},
-            "sample": lambda lg: self._sample(lg, g, True, False, True), "advance": (None, self.rows_gen_graphs, None),
-            "eos": eos_rows, "budgets": max_rows, "per_row": True, "proc": True, "moved": None})
+            "sample": sample, "advance": (None, self.row_lp_gen_graphs, "rows") if logprobs else (None, self.rows_gen_graphs, None),
+            "eos": eos_rows, "budgets": max_rows, "per_row": True, "proc": True, "moved": None, "logprobs": logprobs})
 
     @torch.inference_mode()
     def generate(self, input_ids, max_new_tokens, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                  eos_token_id=None, pad_token_id=None, check_every=16, attention_mask=None, repetition_penalty=1.0,
-                 min_new_tokens=0, draft_tokens=0, draft_ngram=3, extend=False):
+                 min_new_tokens=0, draft_tokens=0, draft_ngram=3, extend=False, logprobs=False):
         """input_ids [batch, prompt] -> [batch, prompt + n] int64 on the device, n <= max_new_tokens; rows that emitted an EOS id
         are padded with pad_token_id (default: the first EOS id) from then on, and the run stops once every row has (HF's
         `generate` semantics).  The prompt is prefilled eagerly and token 1 sampled eagerly from its last position; every later
@@ -760,10 +807,22 @@ class GraphedDecoder:
         of its own (`rows_gen_graphs`: per-row positions, processors attached); row r's tokens are those of the call with row r's
         values as scalars.  The loop runs to max(max_new_tokens); a row past its own limit is finished on the device and padded
         with its pad (pad_token_id, default the row's first EOS id), and n is the longest row's count.  With extend=True every
-        row's token index restarts at 1.  Not with draft_tokens (ValueError).  All scalars: the path above, unchanged."""
+        row's token index restarts at 1.  Not with draft_tokens (ValueError).  All scalars: the path above, unchanged.
+        logprobs=True: the result is unchanged and `last_logprobs` is set to fp32 [batch, n] on the device, aligned with the new
+        columns of the result: the log-probability of each generated token under the model's OWN distribution (log-softmax of the
+        raw logits: temperature, top_k / top_p, repetition_penalty and min_new_tokens are not applied -- what serving APIs return
+        as `logprobs`).  A row's slots past its real tokens -- the pads after its EOS or its own max_new_tokens, every slot of an
+        idle row -- hold 0.0.  The values are computed on the device by a launch recorded behind the sampler, in graph families of
+        their own; a call without logprobs sets `last_logprobs` to None and runs exactly the graphs it ran before.  Not with
+        draft_tokens (ValueError)."""
         input_ids = input_ids.to(self.device)
         if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
             raise ValueError(f"input_ids must be [{self.batch}, prompt], got {tuple(input_ids.shape)}")
+        logprobs = bool(logprobs)
+        if logprobs and draft_tokens:
+            raise ValueError("generate: logprobs is not available with draft_tokens (a speculative step emits a variable number "
+                             "of tokens per replay)")
+        self.last_logprobs = None
         per_row = {"do_sample": do_sample, "temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed,
                    "max_new_tokens": max_new_tokens, "repetition_penalty": repetition_penalty, "min_new_tokens": min_new_tokens}
         eos_per_row = (eos_token_id is not None and ops.is_seq(eos_token_id)
@@ -773,7 +832,7 @@ class GraphedDecoder:
                 raise ValueError("generate: draft_tokens does not take per-row arguments (speculative decoding is one greedy "
                                  "request per batch)")
             return self._generate_rows(input_ids, per_row, eos_token_id, pad_token_id, max(1, int(check_every)), attention_mask,
-                                       extend)
+                                       extend, logprobs)
         max_new_tokens, check_every = int(max_new_tokens), max(1, int(check_every))
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
@@ -796,14 +855,47 @@ class GraphedDecoder:
         greedy = not do_sample or float(temperature) <= 0
         logits, idle = self._first_logits(input_ids, attention_mask, extend)
         before = self._gen
-        g = self._gen_state(logits.shape[-1], max_new_tokens)
+        g = self._gen_state(logits.shape[-1], max_new_tokens, logprobs=logprobs)
         moved = before["history"] if before is not None and before is not g and before["vocab"] == g["vocab"] else None
         # Graphs and sampler kernels: without the processors the sampler is launched without proc / history (the kernels that
         # read neither) and captured into gen_graphs / row_gen_graphs; attaching them always would give the same tokens at
-        # repetition_penalty = 1, slower.  greedy: one pass only, in graphs of its own key.
+        # repetition_penalty = 1, slower.  greedy: one pass only, in graphs of its own key.  logprobs: the same sampler call with
+        # the log-prob launch behind it, in lp_gen_graphs / row_lp_gen_graphs.
+        def sample(lg):
+            self._sample(lg, g, False, greedy, proc)
+            if logprobs:
+                self._logprob(lg, g)
+
+        if logprobs:
+            advance = (self.lp_gen_graphs, self.row_lp_gen_graphs, (greedy, proc))
+        else:
+            advance = (self.proc_gen_graphs, self.row_proc_gen_graphs, greedy) if proc else (self.gen_graphs, self.row_gen_graphs, greedy)
         return self._generate_loop(input_ids, logits, idle, extend, check_every, {
-            "g": g, "words": {"params": params, "proc": proc_bytes} if proc else {"params": params},
-            "sample": lambda lg: self._sample(lg, g, False, greedy, proc),
-            "advance": (self.proc_gen_graphs, self.row_proc_gen_graphs, greedy) if proc else (self.gen_graphs, self.row_gen_graphs, greedy),
-            "eos": [eos] * self.batch, "budgets": [max_new_tokens] * self.batch, "per_row": False, "proc": proc,
-            "moved": moved})
+            "g": g, "words": {"params": params, "proc": proc_bytes} if proc else {"params": params}, "sample": sample,
+            "advance": advance, "eos": [eos] * self.batch, "budgets": [max_new_tokens] * self.batch, "per_row": False, "proc": proc,
+            "moved": moved, "logprobs": logprobs})
+
+    @torch.inference_mode()
+    def score(self, input_ids, attention_mask=None):
+        """input_ids [batch, S] -> fp32 [batch, S] on the device: entry [b, s] is the log-probability of input_ids[b, s] given the
+        row's real tokens before it, under the model's own distribution (ops.token_logprobs: no temperature, no warper, no logit
+        processor).  The first real token of a row and every masked slot (attention_mask as in `prefill`) hold 0.0.  One
+        `prefill` and one launch over its [batch, S, vocab] logits with the labels shifted by one -- no fp32 copy of the logits.
+        The decoder is left exactly where `prefill` leaves it: `step` or `generate(..., extend=True)` can follow.  Perplexity of
+        the batch, with n_scored the number of scored tokens (mask.sum() - batch; S - 1 per row without a mask):
+
+            ppl = torch.exp(-dec.score(ids, mask).sum() / n_scored)"""
+        input_ids = input_ids.to(self.device)
+        if input_ids.dim() != 2 or input_ids.shape[0] != self.batch or input_ids.shape[1] < 1:
+            raise ValueError(f"input_ids must be [{self.batch}, S >= 1], got {tuple(input_ids.shape)}")
+        logits = self.prefill(input_ids, attention_mask)
+        # slot s scores the token at s + 1; -1 (an ignored slot) in the last one and wherever either side is masked
+        labels = torch.full(input_ids.shape, -1, dtype=torch.int64, device=self.device)
+        labels[:, :-1] = input_ids[:, 1:]
+        if attention_mask is not None:
+            real = torch.as_tensor(attention_mask).to(self.device) != 0
+            labels[:, :-1].masked_fill_(~(real[:, 1:] & real[:, :-1]), -1)
+        lp = ops.token_logprobs(logits, labels)
+        out = torch.zeros_like(lp)
+        out[:, 1:] = lp[:, :-1]
+        return out

@@ -1148,10 +1148,10 @@ def _sample_workspace(device, nbytes):
     return ws
 
 
-def _logits_rows(logits):
+def _logits_rows(logits, fn="sample_tokens"):
     """[B, V] or [B, T, V] (the last position) fp16 with unit element stride -> (view [B, V], row stride)."""
     if logits.dtype != torch.float16 or logits.dim() not in (2, 3):
-        raise _lib.AwqHipError(f"sample_tokens: fp16 logits [B, V] or [B, T, V] expected, got {logits.dtype} {tuple(logits.shape)}")
+        raise _lib.AwqHipError(f"{fn}: fp16 logits [B, V] or [B, T, V] expected, got {logits.dtype} {tuple(logits.shape)}")
     rows = logits[:, -1, :] if logits.dim() == 3 else logits
     if rows.stride(1) != 1:
         rows = rows.contiguous()
@@ -1509,3 +1509,66 @@ def ngram_draft(params, tok, hist, n_hist):
     with torch.cuda.device(tok.device):
         a.stream = _stream()
         _lib.check(_lib.lib().awq_ngram_draft(ctypes.byref(a)), "awq_ngram_draft")
+
+
+# ---- token log-probabilities (csrc/logprob.hip) ----------------------------------------------------------------------------------
+
+def _logprob_call(rows, row_stride, R, V, ids, ids_stride, out, out_stride, slot, out_cap):
+    a = _lib.AwqLogprobArgs()
+    a.logits, a.logits_stride, a.ids, a.ids_stride = _ptr(rows), row_stride, _ptr(ids), ids_stride
+    a.out, a.out_stride, a.slot, a.out_cap = _ptr(out), out_stride, _ptr(slot), out_cap
+    a.R, a.V = R, V
+    with torch.cuda.device(rows.device):
+        a.stream = _stream()
+        rc = _lib.lib().awq_token_logprobs(ctypes.byref(a))
+    _lib.check(rc, "awq_token_logprobs")
+
+
+def token_logprobs_launch(logits, ids, out, slot=None):
+    """The raw launch (no validation beyond dtypes, no sync), on buffers the caller owns: logits fp16 [R, V] (or the last position
+    of [R, T, V]), ids int64 with one element per row (any row stride), out fp32 [R] -- or, with slot (int32 [R]), out fp32
+    [R, cap]: row r writes out[r, slot[r]] (dropped at slot[r] >= cap) and slot[r] += 1.  Capturable."""
+    rows, rs = _logits_rows(logits, "token_logprobs_launch")
+    _require_gpu(rows, ids, out, slot)
+    if ids.dtype != torch.int64 or out.dtype != torch.float32 or (slot is not None and slot.dtype != torch.int32):
+        raise _lib.AwqHipError("token_logprobs_launch: ids int64, out fp32 and slot int32 expected")
+    R, V = rows.shape
+    _logprob_call(rows, rs, R, V, ids, ids.stride(0) if ids.dim() else 1, out, out.stride(0) if out.dim() else 1, slot,
+                  out.shape[1] if slot is not None and out.dim() == 2 else (1 if slot is not None else 0))
+    return out
+
+
+def token_logprobs(logits, ids, out=None):
+    """log p(ids | logits) per row -> fp32 of ids' shape: (x[id] - max x) - log sum exp(x - max x) over the fp16 logits [..., V]
+    cast to fp32 (csrc/logprob.hip, one block per row; no fp32 copy of the logits is made).  This is the model's own
+    distribution: temperature, top-k / top-p and the logit processors are NOT applied -- what perplexity needs and what serving
+    APIs return as `logprobs`.  ids int64 with the leading shape of logits; id < 0 marks an ignored slot (shifted labels, pads,
+    masked positions) and gives 0.0; id >= V gives NaN, as does a row holding NaN or +inf or nothing but -inf; -inf logits are
+    legal (the id's own: -inf).  The last dimension of logits must be contiguous; leading dimensions that do not collapse to one
+    row stride are made contiguous once."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(ids, torch.Tensor):
+        raise _lib.AwqHipError("token_logprobs: tensors expected")
+    if logits.dtype != torch.float16 or logits.dim() < 1:
+        raise _lib.AwqHipError(f"token_logprobs: fp16 logits [..., V] expected, got {logits.dtype} {tuple(logits.shape)}")
+    if ids.dtype != torch.int64 or tuple(ids.shape) != tuple(logits.shape[:-1]):
+        raise _lib.AwqHipError(f"token_logprobs: ids must be int64 {tuple(logits.shape[:-1])}, got {ids.dtype} {tuple(ids.shape)}")
+    V = int(logits.shape[-1])
+    if not 1 <= V <= 1 << 20:
+        raise _lib.AwqHipError(f"token_logprobs: vocabulary {V} outside 1 .. 2^20")
+    if V > 1 and logits.stride(-1) != 1:
+        raise _lib.AwqHipError("token_logprobs: the last dimension of logits must be contiguous")
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != tuple(ids.shape) or not out.is_contiguous()):
+        raise _lib.AwqHipError(f"token_logprobs: out must be contiguous fp32 {tuple(ids.shape)}")
+    _require_gpu(logits, ids, out)
+    lead = [(n, s) for n, s in zip(logits.shape[:-1], logits.stride()[:-1]) if n != 1]
+    R = math.prod(logits.shape[:-1])
+    if R > 0 and not all(so == ni * si for (_, so), (ni, si) in zip(lead, lead[1:])):
+        logits, lead = logits.contiguous(), [(R, V)]
+    stride = lead[-1][1] if lead else V
+    if stride < V:  # (expanded rows and the like)
+        logits, stride = logits.contiguous(), V
+    if out is None:
+        out = torch.empty(ids.shape, dtype=torch.float32, device=logits.device)
+    if R:
+        _logprob_call(logits, stride, R, V, ids.contiguous(), 1, out, 1, None, 0)
+    return out

@@ -803,6 +803,31 @@ typedef struct AwqSpecArgs {
 AWQ_EXPORT int awq_spec_accept(const AwqSpecArgs* args);
 AWQ_EXPORT int awq_ngram_draft(const AwqSpecArgs* args);
 
+/* ---- token log-probabilities (csrc/logprob.hip) -------------------------------------------------------------------------------
+ * awq_token_logprobs: for each of R rows, out = (x[id] - m) - log sum_i exp(x_i - m) in fp32, x the row's V fp16 logits cast to
+ * fp32 and m their maximum: the log-probability of token `id` under the model's OWN distribution (no temperature, top-k / top-p or
+ * logit processor is applied).  -inf logits are legal and contribute 0; the id's own logit -inf gives -inf; a row holding NaN or
+ * +inf, or all -inf, gives NaN; id < 0 is an ignored slot and writes 0.0f (shifted labels, pads, masked positions; the row is not
+ * read); id >= V gives NaN.  Row r's logits start at logits + r * logits_stride (elements; any alignment: 16-byte loads are used
+ * where base and stride allow, element loads otherwise, and no byte outside a row's V elements is read), its id is
+ * ids[r * ids_stride].  slot == NULL: the result goes to out[r * out_stride].  slot [R] int32: to out[r * out_stride + slot[r]]
+ * -- dropped unless 0 <= slot[r] < out_cap -- and then slot[r] += 1 (a captured launch fills a ring of results).  One launch, one
+ * block per row, no workspace, capturable.  1 <= V <= 2^20, 0 <= R <= 2^31 - 1, logits_stride >= V (AWQ_ERR_BAD_SHAPE otherwise);
+ * R == 0 returns AWQ_OK without a launch; a NULL struct, logits, ids or out with R > 0 is AWQ_ERR_NULL. */
+typedef struct AwqLogprobArgs {
+    const uint16_t* logits; /* fp16 */
+    int64_t logits_stride;  /* elements between rows (>= V) */
+    const int64_t* ids;
+    int64_t ids_stride;     /* elements between rows */
+    float* out;
+    int64_t out_stride;     /* elements between rows */
+    int32_t* slot;          /* [R] or NULL */
+    int64_t out_cap;        /* with slot: columns of out a row may write */
+    int64_t R, V;
+    void* stream;
+} AwqLogprobArgs;
+AWQ_EXPORT int awq_token_logprobs(const AwqLogprobArgs* args);
+
 #ifdef __cplusplus
 }
 #endif
