@@ -1,35 +1,37 @@
 """QuantAttentionFused for MI355X (reference: awq/modules/fused/attn.py:127-312).
 
-Same constructor arguments and the same forward contract: `forward(hidden_states)` runs the fused
-qkv projection, rotary embedding, the KV-cache update, attention and `o_proj`, advances
-`start_pos`, and returns `(attn_output, attention_weight, past_key_value)`.
+Same constructor arguments and the same forward contract: `forward(hidden_states)` runs the fused qkv projection, rotary
+embedding, the KV-cache update, attention and `o_proj`, advances `start_pos`, and returns `(attn_output, attention_weight,
+past_key_value)`.  Everything after the projection is `forward_qkv`: it states what the call is as ONE `AttnStep` (`_step`), and
+the append, the rows attended over and the attention kernel are read off that description and nothing else:
 
-MI355X-first differences:
-  * RoPE + cache update is ONE kernel on the fused qkv output (`awq_rope_kv_append`) instead of
-    a complex-multiply in torch followed by two slice assignments (attn.py:54-87, cache.py:40-45);
-  * decode (one new token per sequence) runs `awq_decode_attention` over the cache -- the role
-    flash_attn_with_kvcache has in the reference (attn.py:286-302).  Prefill (seqlen > 1) uses
-    torch's scaled_dot_product_attention, where the reference calls flash_attn_func (:277-285):
-    vendor attention is plumbing here, the int4 projections are the product;
-  * `use_device_positions(pos, length)`: start position and length live in device int32 tensors so
-    that one captured hipGraph can be replayed for every decode step; with `per_row=True` they hold one word per sequence
-    (batches of prompts of different lengths) and the decode steps call the *_rows forms of the kernels.
-  * the feature surface of attn.py:89-125,159-203 rides on the same kernels: `attention_shapes` (how the fused row is viewed and
-    sliced, awq/utils/fused_utils.py:165-201) and `q_norm` / `k_norm` are applied to the projection's output, which is then put
-    back into the q | k | v head order the kernels read; ALiBi models skip the rotation (rotary width 0 in the append kernel)
-    and pass their slopes, `attn_logit_softcapping` its cap, to `awq_decode_attention_ex` -- what the reference hands
-    flash_attn_with_kvcache as `alibi_slopes=` / `softcap=` (attn.py:286-302).  Prefill with either modifier computes the
-    scores in torch (fp32), where the reference calls flash_attn_func with the same arguments (attn.py:277-285).
-  * `kv_cache_dtype="fp8"` (opt-in; default "fp16"): the cache holds e4m3 codes + one fp32 scale per row (WindowedCache, format in
-    include/awq_hip.h); appends and decode attention run the *_fp8 kernels.  Prefill appends in fp8, dequantizes rows
-    [0, start_pos + S) into an fp16 workspace and runs the unchanged prefill attention on it, so a prompt attends to the same
-    quantized values its decode steps will read.  Only the native head shapes take it (head_dim 128, 1 / 2 / 4 / 8 query heads per
-    KV head): other shapes slice the cache in torch and are refused at construction.
-  * `extend_rows = (pos_rows, count_rows, max_end)` (set by the caller, like `verify_rows`): prefill at per-row positions -- a
-    second turn of a conversation, a new prompt in a finished row's slot.  Append with per-row counts, then
-    `awq_prefill_attention_rows`; no reference counterpart (its prefill ignores the cache)."""
+  kind     asked for by           positions from                     append (rope_kv_append)   attention                   start_pos
+  prefill  S > 1                  host start_pos                     S rows at start_pos       prefill_attention [1]       += S
+  decode   S == 1                 host start_pos, or                 one row at the position   decode_attention; append    += 1
+                                  shared words (pos, len), or                                  and attention in ONE launch
+                                  per-row words [B]                                            (decode_attention_rope) [2]
+  verify   request="verify"       per-row words                      T rows at pos_b           verify_attention_rows       stays
+  extend   request=(pos, count,   per-row pos and count, host bound  count_b rows at pos_b     prefill_attention_rows      stays
+           max_end)               max_end                                                      (max_end == 0: zeros)
+
+  [1] head_dim 128 and PREFILL_KERNEL; otherwise the vendor's attention (`_attend_vendor`: fp32 matmul-softmax when the scores
+      carry a soft cap or ALiBi, else scaled_dot_product_attention), which decode takes too on a non-native head shape.
+  [2] one launch for rotation, append and attention: native head shape, full rotary, FUSE_ROPE_INTO_ATTENTION, no modifier.
+
+  * native head shape: head_dim 128 and 1, 2, 4 or 8 query heads per KV head (what the hand-written decode, verify and rows
+    kernels take).  Per-row words, verify, extend and the fp8 cache need it.
+  * `use_device_positions(pos, len, per_row, bound)`: decode positions live in device int32 words so that one captured hipGraph
+    serves every step; a launch whose length only the device knows is sized for `bound` (default: the cache window).  verify and
+    extend are never inferred from S: the caller asks for them, owns the positions and keeps only the rows it wants.
+  * `attention_shapes` and `q_norm` / `k_norm` (attn.py:89-125,159-203) are applied to the projection's output, which is put back
+    into the q | k | v head order the kernels read (`_qkv_rows`); ALiBi models skip the rotation (rotary width 0 in the append) and
+    pass their slopes, `attn_logit_softcapping` its cap, to the kernels (the reference: `alibi_slopes=` / `softcap=`, :286-302).
+  * `kv_cache_dtype="fp8"` (opt-in): the cache holds e4m3 codes + one fp32 scale per row (WindowedCache, format in
+    include/awq_hip.h); append and decode run the *_fp8 kernels.  prefill and extend append codes, dequantize rows [0, end) into an
+    fp16 workspace (`_kv_rows`) and attend over that, so a prompt sees the values its decode steps will read."""
 import math
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -83,6 +85,32 @@ class ALiBi(nn.Module):
         return scores
 
 
+class AttnStep(NamedTuple):
+    """What one forward_qkv call is (QuantAttentionFused._step builds it; the table in the module docstring reads it)."""
+    kind: str             # "prefill" | "decode" | "verify" | "extend"
+    seqlen: int
+    start: int            # the host's start_pos; 0 where the caller owns the positions (verify, extend)
+    pos: object = None    # device position word(s) -- None: the positions are `start`, on the host
+    len: object = None    # device length word(s) after the append (decode)
+    rows: bool = False    # pos / len (/ count) hold one word per sequence, not one shared word
+    count: object = None  # extend: new tokens per sequence
+    bound: object = None  # what a launch with a device-side length is sized for (extend: max_end); None on the host
+
+    @property
+    def advance(self):
+        """the module's start_pos moves by seqlen (verify and extend: the caller owns the positions)"""
+        return self.kind in ("prefill", "decode")
+
+    @property
+    def end(self):
+        """host bound of the cache rows this call may see"""
+        return self.bound if self.kind == "extend" else self.start + self.seqlen
+
+    def word(self, w):
+        """(shared word, per-row words): the two keyword slots the kernels have for one device word"""
+        return (None, w) if self.rows else (w, None)
+
+
 class QuantAttentionFused(nn.Module):
     FUSE_ROPE_INTO_ATTENTION = True  # decode steps, head_dim 128, full rotary
     PREFILL_KERNEL = True            # prefill steps, head_dim 128: csrc/prefill_attn.hip (False: the vendor's attention, for A/B runs)
@@ -108,8 +136,7 @@ class QuantAttentionFused(nn.Module):
         self.attention_shapes = get_attention_shapes(attention_shapes, n_heads, n_kv_heads, self.head_dim)
         if kv_cache_dtype not in ("fp16", "fp8"):
             raise ValueError(f"QuantAttentionFused: kv_cache_dtype must be 'fp16' or 'fp8', got {kv_cache_dtype!r}")
-        if kv_cache_dtype == "fp8" and not (self.head_dim == 128 and n_heads % self.n_kv_heads == 0
-                                            and self.n_kv_groups in (1, 2, 4, 8)):
+        if kv_cache_dtype == "fp8" and not (self.native and n_heads % self.n_kv_heads == 0):
             raise ValueError(f"QuantAttentionFused: kv_cache_dtype='fp8' needs head_dim 128 and 1, 2, 4 or 8 query heads per KV head "
                              f"(got head_dim {self.head_dim}, {n_heads} / {self.n_kv_heads} heads)")
         self.kv_cache_dtype = kv_cache_dtype
@@ -132,25 +159,30 @@ class QuantAttentionFused(nn.Module):
             self.rotary_dim = int(self.head_dim * partial_rotary_factor)
             self.rope = RoPE(self.rotary_dim, max_seq_len, dev, rope_theta)
             self.is_neox = True
-        self._pos_dev = None
-        self._len_dev = None
+        self._pos_dev = self._len_dev = self._bound = None
         self._per_row = False
-        self.verify_rows = False  # set by the caller of a speculative verify step (LlamaLikeModel.forward(verify=True))
-        self.extend_rows = None   # (pos_rows, count_rows, max_end): set by the caller of an extend step (forward(extend=...))
 
-    def use_device_positions(self, pos_dev, len_dev, per_row=False):
+    @property
+    def native(self):
+        """the head shapes the hand-written decode, verify and rows kernels take; others run the vendor's attention"""
+        return self.head_dim == 128 and self.n_kv_groups in (1, 2, 4, 8)
+
+    @property
+    def modified(self):
+        """the scores carry a bias (ALiBi) or a cap: no fused decode launch, fp32 scores on the vendor path"""
+        return self.alibi is not None or self.attn_logit_softcapping > 0
+
+    def use_device_positions(self, pos_dev, len_dev, per_row=False, bound=None):
         """pos_dev / len_dev: int32 device tensors of one element (shared by all layers) holding the
         start position and the cache length after the append; the caller advances them.  per_row=True: both are [B], one
-        position and one length per sequence (decode steps only; the host-side start_pos of prefill is not per row)."""
+        position and one length per sequence (decode steps only; the host-side start_pos of prefill is not per row).
+        bound: what a launch that reads its length from the device is sized for -- the cache window, or the tighter bound of a
+        caller that knows the context on the host (modules/fused/decode.py: one hipGraph per length bucket).  (None, None): back
+        to the host's start_pos, and the bound goes with the words."""
         if per_row and (pos_dev is None or len_dev is None):
             raise ValueError("use_device_positions: per_row needs both the position and the length words")
         self._pos_dev, self._len_dev, self._per_row = pos_dev, len_dev, bool(per_row)
-
-    def _len_bound(self):
-        """What a decode launch with a DEVICE-side length is sized for: the cache window, or the tighter bound a caller that
-        knows the context on the host has set (`decode_len_bound`, modules/fused/decode.py: one hipGraph per length bucket)."""
-        b = getattr(self, "decode_len_bound", None)
-        return self.max_seq_len if b is None else max(1, min(int(b), self.max_seq_len))
+        self._bound = None if pos_dev is None else self.max_seq_len if bound is None else max(1, min(int(bound), self.max_seq_len))
 
     def _resize_cache(self, bsz):
         if bsz != self.cache_batch_size:
@@ -161,13 +193,13 @@ class QuantAttentionFused(nn.Module):
             self.cache_batch_size = bsz
             self.start_pos = 0  # the reference resets on a batch-size change (attn.py:208-218)
 
-    def forward(self, hidden_states, *args, **kwargs):
+    def forward(self, hidden_states, *args, request=None, **kwargs):
         bsz, seqlen, _ = hidden_states.shape
         self._resize_cache(bsz)
         xqkv = self.qkv_proj(hidden_states)
         if xqkv.dtype != torch.float16:
             xqkv = xqkv.half()
-        return self.forward_qkv(xqkv)
+        return self.forward_qkv(xqkv, request=request)
 
     def _qkv_rows(self, xqkv):
         """The projection's output as the kernels read it: [B, S, (Hq + 2 Hkv) * D], q heads | k heads | v heads.  Custom
@@ -201,142 +233,109 @@ class QuantAttentionFused(nn.Module):
         scores = scores.masked_fill(kpos > qpos, float("-inf"))
         return torch.matmul(torch.softmax(scores, dim=-1), v.float()).to(torch.float16)
 
-    def _verify_qkv(self, xqkv, apply_o_proj):
-        """The verify step of speculative decoding (asked for explicitly through `verify_rows`, never inferred from seqlen, so
-        chunked prefill keeps its meaning): T = 2 .. 8 new tokens per sequence at the per-row device positions.  Rows
-        pos_b .. pos_b + T - 1 are appended, query (b, j) attends over rows <= pos_b + j (ops.verify_attention_rows).  The
-        host-side start_pos is not advanced: the decoder owns the positions and keeps only the rows it accepts."""
-        bsz, seqlen, _ = xqkv.shape
-        if self.kv_cache_dtype == "fp8":
-            raise NotImplementedError('speculative decoding: kv_cache_dtype="fp8" is not supported (verify_attention_rows '
-                                      "reads fp16 caches)")
-        if not (self._per_row and self._pos_dev is not None):
-            raise RuntimeError("a verify step needs per-row device positions (use_device_positions(..., per_row=True))")
-        native = self.head_dim == 128 and self.n_kv_groups in (1, 2, 4, 8)
-        if not native or self.alibi is not None or self.attn_logit_softcapping > 0 or not 2 <= seqlen <= 8:
-            raise NotImplementedError("a verify step takes 2 .. 8 tokens, head_dim 128, 1, 2, 4 or 8 query heads per KV head, "
-                                      "no ALiBi and no soft cap")
-        xq = ops.rope_kv_append(xqkv, self.cache.k, self.cache.v, self.rope.cos, self.rope.sin, 0, self.n_heads, self.n_kv_heads,
-                                self.head_dim, self.rotary_dim, pos_rows=self._pos_dev)
-        out = ops.verify_attention_rows(xq, self.cache.k, self.cache.v, self._pos_dev, max_len=max(seqlen, self._len_bound()))
-        heads = out.reshape(bsz, seqlen, -1)
-        attn_output = self.o_proj(heads) if apply_o_proj else heads
-        return attn_output, heads, [torch.zeros(1, 1, self.start_pos, 1)]
+    def _step(self, seqlen, request):
+        """The one place that reads the configured words and the call: request None (prefill for S > 1, else decode), "verify"
+        (T = 2 .. 8 tokens per sequence at the per-row words: speculative decoding) or (pos_rows, count_rows, max_end) (extend:
+        sequence b's first count_rows[b] tokens at cache rows pos_rows[b] .., max_end the host's bound of their sums)."""
+        if request == "verify":
+            if self.kv_cache_dtype == "fp8":
+                raise NotImplementedError('speculative decoding: kv_cache_dtype="fp8" is not supported (verify_attention_rows '
+                                          "reads fp16 caches)")
+            if not (self._per_row and self._pos_dev is not None):
+                raise RuntimeError("a verify step needs per-row device positions (use_device_positions(..., per_row=True))")
+            if not self.native or self.modified or not 2 <= seqlen <= 8:
+                raise NotImplementedError("a verify step takes 2 .. 8 tokens, head_dim 128, 1, 2, 4 or 8 query heads per KV head, "
+                                          "no ALiBi and no soft cap")
+            return AttnStep("verify", seqlen, 0, self._pos_dev, rows=True, bound=max(seqlen, self._bound))
+        if request is not None:
+            pos_rows, count_rows, max_end = request
+            max_end = int(max_end)
+            if not self.native:
+                raise NotImplementedError("an extend step takes head_dim 128 and 1, 2, 4 or 8 query heads per KV head")
+            if not 0 <= max_end <= self.max_seq_len:
+                raise ValueError(f"extend: max_end {max_end} outside the cache window {self.max_seq_len}")
+            return AttnStep("extend", seqlen, 0, pos_rows, rows=True, count=count_rows, bound=max_end)
+        if seqlen > 1 or self._pos_dev is None:  # (prefill is at the host's start_pos whether words are set or not)
+            return AttnStep("prefill" if seqlen > 1 else "decode", seqlen, self.start_pos)
+        return AttnStep("decode", seqlen, self.start_pos, self._pos_dev, self._len_dev, self._per_row, bound=self._bound)
 
-    def _extend_qkv(self, xqkv, apply_o_proj):
-        """Prefill at per-row positions (asked for explicitly through `extend_rows` = (pos_rows, count_rows, max_end), never
-        inferred from seqlen): sequence b's first count_rows[b] tokens are appended at cache rows pos_rows[b] .. and query (b, s)
-        attends over rows <= pos_rows[b] + s (ops.prefill_attention_rows); the slots behind them write nothing and their output
-        is zeros.  max_end is the host's bound of pos_rows[b] + count_rows[b].  An fp8 cache appends codes, dequantizes rows
-        [0, max_end) and attends over those, as the shared prefill does.  The host-side start_pos is not advanced: the caller
-        owns the positions."""
-        bsz, seqlen, _ = xqkv.shape
-        pos_rows, count_rows, max_end = self.extend_rows
-        max_end = int(max_end)
-        if not (self.head_dim == 128 and self.n_kv_groups in (1, 2, 4, 8)):
-            raise NotImplementedError("an extend step takes head_dim 128 and 1, 2, 4 or 8 query heads per KV head")
-        if not 0 <= max_end <= self.max_seq_len:
-            raise ValueError(f"extend: max_end {max_end} outside the cache window {self.max_seq_len}")
-        xq = ops.rope_kv_append(xqkv, self.cache.k, self.cache.v, self.rope.cos, self.rope.sin, 0, self.n_heads, self.n_kv_heads,
-                                self.head_dim, self.rotary_dim, pos_rows=pos_rows, k_scale=self.cache.k_scale,
-                                v_scale=self.cache.v_scale, count_rows=count_rows)
-        k_rows, v_rows = self.cache.k, self.cache.v
-        if self.kv_cache_dtype == "fp8" and max_end > 0:
-            k_rows = ops.kv_dequant_fp8(self.cache.k, self.cache.k_scale, max_end, bsz)
-            v_rows = ops.kv_dequant_fp8(self.cache.v, self.cache.v_scale, max_end, bsz)
-        if max_end == 0:  # no row has a token and none a context: nothing to attend
-            out = torch.zeros_like(xq)
-        else:
-            out = ops.prefill_attention_rows(xq, k_rows, v_rows, pos_rows, count_rows, max_end, softcap=self.attn_logit_softcapping,
-                                             alibi_slopes=self.alibi.slopes if self.alibi is not None else None)
-        heads = out.reshape(bsz, seqlen, -1)
-        attn_output = self.o_proj(heads) if apply_o_proj else heads
-        return attn_output, heads, [torch.zeros(1, 1, self.start_pos, 1)]
+    def _kv_rows(self, step, bsz):
+        """what a prefill-type kernel attends over: the caches themselves, or rows [0, end) of an fp8 cache dequantized to fp16
+        [B, end, Hkv, 128]"""
+        c = self.cache
+        if self.kv_cache_dtype != "fp8" or step.kind == "decode":
+            return c.k, c.v
+        return ops.kv_dequant_fp8(c.k, c.k_scale, step.end, bsz), ops.kv_dequant_fp8(c.v, c.v_scale, step.end, bsz)
 
-    def forward_qkv(self, xqkv, apply_o_proj=True):
+    def _attend_vendor(self, step, xq, k_rows, v_rows, bsz):
+        """head shapes the hand-written kernels do not take (e.g. 24 / 8 heads, head_dim 64), or PREFILL_KERNEL off: the vendor's
+        attention over rows [0, end) -> [B, S, Hq, D]"""
+        q = xq.transpose(1, 2)                                      # [B, Hq, S, D]
+        k = k_rows[:bsz, :step.end].transpose(1, 2)                 # [B, Hkv, T, D]
+        v = v_rows[:bsz, :step.end].transpose(1, 2)
+        if self.n_kv_groups > 1:
+            k = k.repeat_interleave(self.n_kv_groups, dim=1)
+            v = v.repeat_interleave(self.n_kv_groups, dim=1)
+        if self.modified:  # fp32 matmul softmax when the scores carry a bias or a cap
+            out = self._attend_torch(q, k, v, step.start)
+        elif step.kind == "decode":
+            out = F.scaled_dot_product_attention(q, k, v)
+        elif step.start == 0:
+            out = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+        else:  # chunked prefill: query s sees cache rows <= start_pos + s
+            mask = torch.ones((step.seqlen, step.end), dtype=torch.bool, device=q.device).tril(diagonal=step.start)
+            out = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
+        return out.transpose(1, 2)
+
+    def _attend(self, step, xq, bsz):
+        """xq [B, S, Hq, D], rotated, its k / v rows already in the cache -> the heads' output"""
+        c, softcap = self.cache, self.attn_logit_softcapping
+        slopes = self.alibi.slopes if self.alibi is not None else None
+        if step.kind == "verify":  # query (b, j) attends over rows <= pos_b + j
+            return ops.verify_attention_rows(xq, c.k, c.v, step.pos, max_len=step.bound)
+        if step.kind == "extend" and step.end == 0:  # no row has a token and none a context: nothing to attend
+            return torch.zeros_like(xq)
+        k_rows, v_rows = self._kv_rows(step, bsz)
+        if step.kind == "extend":  # query (b, s) attends over rows <= pos_b + s; the slots behind count_b are zeros
+            return ops.prefill_attention_rows(xq, k_rows, v_rows, step.pos, step.count, step.end, softcap=softcap, alibi_slopes=slopes)
+        if step.kind == "prefill" and self.head_dim == 128 and self.n_heads % self.n_kv_heads == 0 and self.PREFILL_KERNEL:
+            # the hand-written flash-style kernel (csrc/prefill_attn.hip; the reference's flash_attn_func call, attn.py:269-277),
+            # chunked prefill, GQA, ALiBi and the soft cap included -- no mask tensor, no repeat_interleave copy of the cache
+            return ops.prefill_attention(xq, k_rows, v_rows, step.start, softcap=softcap, alibi_slopes=slopes)
+        if step.kind == "decode" and self.native:
+            len_dev, len_rows = step.word(step.len)
+            # max_len only with a device length (step.bound is None on the host): the launcher sizes the split from seq_len then
+            # and never reads it (csrc/decoder.hip, awq_launch_decode_attention)
+            return ops.decode_attention(xq[:, 0], c.k, c.v, step.start + 1, len_dev=len_dev, max_len=step.bound, softcap=softcap,
+                                        alibi_slopes=slopes, len_rows=len_rows, k_scale=c.k_scale, v_scale=c.v_scale)
+        if step.rows:
+            raise NotImplementedError("per-row decode positions need the native decode attention (head_dim 128, "
+                                      "1, 2, 4 or 8 query heads per KV head)")
+        return self._attend_vendor(step, xq, k_rows, v_rows, bsz)
+
+    def forward_qkv(self, xqkv, apply_o_proj=True, request=None):
         """Everything after the qkv projection (the caller may have produced `xqkv` [B, S, (Hq + 2 Hkv) D]
         with the norm folded into the projection).  apply_o_proj=False returns the attention heads' output
-        in place of attn_output (the caller runs o_proj with the residual add in its epilogue)."""
+        in place of attn_output (the caller runs o_proj with the residual add in its epilogue).  request: see `_step`."""
         bsz, seqlen, _ = xqkv.shape
         self._resize_cache(bsz)
         xqkv = self._qkv_rows(xqkv)
-        if self.verify_rows:
-            return self._verify_qkv(xqkv, apply_o_proj)
-        if self.extend_rows is not None:
-            return self._extend_qkv(xqkv, apply_o_proj)
-        device_pos = self._pos_dev is not None and seqlen == 1
-        rows = device_pos and self._per_row  # one position / length word per sequence: the *_rows kernels
-        # the hand-written decode kernels take head_dim 128 and 1, 2, 4 or 8 query heads per KV head; other
-        # shapes (e.g. 24 / 8 heads, 28 / 4) take the vendor path below instead of failing at the first decode step
-        native = self.head_dim == 128 and self.n_kv_groups in (1, 2, 4, 8)
-        modified = self.alibi is not None or self.attn_logit_softcapping > 0  # scores carry a bias or a cap
-        if seqlen == 1 and native and self.rotary_dim == 128 and self.FUSE_ROPE_INTO_ATTENTION and not modified:
-            # decode: rotation, cache append and attention in ONE launch (awq_decode_attention_rope)
-            out = ops.decode_attention_rope(xqkv, self.cache.k, self.cache.v, self.rope.cos, self.rope.sin, self.start_pos,
-                                            self.n_heads, self.n_kv_heads,
-                                            pos_dev=self._pos_dev if device_pos and not rows else None,
-                                            max_len=self._len_bound() if device_pos else None,
-                                            pos_rows=self._pos_dev if rows else None, k_scale=self.cache.k_scale,
-                                            v_scale=self.cache.v_scale)
-            attention_weight = out.reshape(bsz, 1, -1)
-            attn_output = self.o_proj(attention_weight) if apply_o_proj else attention_weight
-            self.start_pos += 1
-            return attn_output, attention_weight, [torch.zeros(1, 1, self.start_pos, 1)]
-        xq = ops.rope_kv_append(xqkv, self.cache.k, self.cache.v, self.rope.cos, self.rope.sin, self.start_pos,
-                                self.n_heads, self.n_kv_heads, self.head_dim, self.rotary_dim,
-                                pos_dev=self._pos_dev if device_pos and not rows else None,
-                                pos_rows=self._pos_dev if rows else None, k_scale=self.cache.k_scale, v_scale=self.cache.v_scale)
-        k_rows, v_rows = self.cache.k, self.cache.v  # what prefill attends over
-        if seqlen > 1 and self.kv_cache_dtype == "fp8":  # the appended rows, dequantized: [B, start_pos + S, Hkv, 128] fp16
-            end = self.start_pos + seqlen
-            k_rows = ops.kv_dequant_fp8(self.cache.k, self.cache.k_scale, end, bsz)
-            v_rows = ops.kv_dequant_fp8(self.cache.v, self.cache.v_scale, end, bsz)
-        if seqlen > 1 and self.head_dim == 128 and self.n_heads % self.n_kv_heads == 0 and self.PREFILL_KERNEL:
-            # prefill: the hand-written flash-style kernel (csrc/prefill_attn.hip; the reference's flash_attn_func call, attn.py:269-277),
-            # chunked prefill, GQA, ALiBi and the soft cap included -- no mask tensor, no repeat_interleave copy of the cache
-            out = ops.prefill_attention(xq, k_rows, v_rows, self.start_pos, softcap=self.attn_logit_softcapping,
-                                        alibi_slopes=self.alibi.slopes if self.alibi is not None else None)
-            output = out.reshape(bsz, seqlen, -1)
-        elif seqlen > 1:  # other head sizes: the vendor's attention (fp32 matmul softmax when the scores carry a bias or a cap)
-            end = self.start_pos + seqlen
-            q = xq.transpose(1, 2)                                  # [B, Hq, S, D]
-            k = k_rows[:bsz, :end].transpose(1, 2)                  # [B, Hkv, T, D]
-            v = v_rows[:bsz, :end].transpose(1, 2)
-            if self.n_kv_groups > 1:
-                k = k.repeat_interleave(self.n_kv_groups, dim=1)
-                v = v.repeat_interleave(self.n_kv_groups, dim=1)
-            if modified:
-                out = self._attend_torch(q, k, v, self.start_pos)
-            elif self.start_pos == 0:
-                out = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-            else:  # chunked prefill: query s sees cache rows <= start_pos + s
-                mask = torch.ones((seqlen, end), dtype=torch.bool, device=q.device).tril(diagonal=self.start_pos)
-                out = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
-            output = out.transpose(1, 2).reshape(bsz, seqlen, -1)
+        step = self._step(seqlen, request)
+        c, rope = self.cache, self.rope
+        pos_dev, pos_rows = step.word(step.pos)
+        if (step.kind == "decode" and self.native and self.rotary_dim == 128 and self.FUSE_ROPE_INTO_ATTENTION
+                and not self.modified):
+            # rotation, cache append and attention in ONE launch (awq_decode_attention_rope); max_len as in `_attend`
+            out = ops.decode_attention_rope(xqkv, c.k, c.v, rope.cos, rope.sin, step.start, self.n_heads, self.n_kv_heads,
+                                            pos_dev=pos_dev, max_len=step.bound, pos_rows=pos_rows, k_scale=c.k_scale,
+                                            v_scale=c.v_scale)
         else:
-            if not native:  # the hand-written kernel is specialised (head_dim, GQA ratio); other shapes take the vendor path
-                if rows:
-                    raise NotImplementedError("per-row decode positions need the native decode attention (head_dim 128, "
-                                              "1, 2, 4 or 8 query heads per KV head)")
-                k = self.cache.k[:bsz, : self.start_pos + 1].transpose(1, 2)
-                v = self.cache.v[:bsz, : self.start_pos + 1].transpose(1, 2)
-                if self.n_kv_groups > 1:
-                    k = k.repeat_interleave(self.n_kv_groups, dim=1)
-                    v = v.repeat_interleave(self.n_kv_groups, dim=1)
-                if modified:
-                    output = self._attend_torch(xq.transpose(1, 2), k, v, self.start_pos).transpose(1, 2).reshape(bsz, 1, -1)
-                else:
-                    output = F.scaled_dot_product_attention(xq.transpose(1, 2), k, v).transpose(1, 2).reshape(bsz, 1, -1)
-            else:
-                out = ops.decode_attention(xq[:, 0], self.cache.k, self.cache.v, self.start_pos + 1,
-                                           len_dev=self._len_dev if device_pos and not rows else None, max_len=self._len_bound(),
-                                           softcap=self.attn_logit_softcapping,
-                                           alibi_slopes=self.alibi.slopes if self.alibi is not None else None,
-                                           len_rows=self._len_dev if rows else None, k_scale=self.cache.k_scale,
-                                           v_scale=self.cache.v_scale)
-                output = out.reshape(bsz, 1, -1)
-        attention_weight = output
+            xq = ops.rope_kv_append(xqkv, c.k, c.v, rope.cos, rope.sin, step.start, self.n_heads, self.n_kv_heads, self.head_dim,
+                                    self.rotary_dim, pos_dev=pos_dev, pos_rows=pos_rows, k_scale=c.k_scale, v_scale=c.v_scale,
+                                    count_rows=step.count)
+            out = self._attend(step, xq, bsz)
+        attention_weight = out.reshape(bsz, seqlen, -1)
         attn_output = self.o_proj(attention_weight) if apply_o_proj else attention_weight
-        self.start_pos += seqlen
-        past_key_value = [torch.zeros(1, 1, self.start_pos, 1)]
-        return attn_output, attention_weight, past_key_value
+        if step.advance:
+            self.start_pos += seqlen
+        return attn_output, attention_weight, [torch.zeros(1, 1, self.start_pos, 1)]

@@ -10,6 +10,18 @@ from .attn import QuantAttentionFused
 from .norm import FasterTransformerRMSNorm
 
 
+def _attn_then_norm_2(block, hidden_states, request):
+    """h = x + attn(norm_1(x)) and norm_2(h) for MixtralBlock and LlamaLikeBlock -> (h, norm_2(h)); the residual add rides on
+    norm_2 where it can (one launch, the sum lands in o_proj's own output buffer)"""
+    attn_output, _, _ = block.attn.forward(hidden_states=block.norm_1(hidden_states), request=request)
+    if (isinstance(block.norm_2, FasterTransformerRMSNorm) and attn_output.dtype == hidden_states.dtype == torch.float16
+            and attn_output.is_contiguous() and hidden_states.is_contiguous()):
+        h = attn_output  # becomes hidden_states + attn_output, in place
+        return h, block.norm_2(hidden_states, residual=h)
+    h = hidden_states.to(attn_output.device) + attn_output
+    return h, block.norm_2(h)
+
+
 class MixtralBlock(nn.Module):
     """Reference: awq/modules/fused/block.py:6-55 -- same constructor, same dataflow
     `h = x + attn(norm_1(x)); out = h + moe(norm_2(h))`, `moe` a FusedSparseMoeBlock (modules/fused/moe.py: routing in one launch,
@@ -31,16 +43,8 @@ class MixtralBlock(nn.Module):
         self.moe = moe
         self.device = dev
 
-    def forward(self, hidden_states):
-        norm_out = self.norm_1(hidden_states)
-        attn_output, _, _ = self.attn.forward(hidden_states=norm_out)
-        if (isinstance(self.norm_2, FasterTransformerRMSNorm) and attn_output.dtype == hidden_states.dtype == torch.float16
-                and attn_output.is_contiguous() and hidden_states.is_contiguous()):
-            h = attn_output  # becomes hidden_states + attn_output, in place in o_proj's own output buffer
-            normed = self.norm_2(hidden_states, residual=h)
-        else:
-            h = hidden_states.to(attn_output.device) + attn_output
-            normed = self.norm_2(h)
+    def forward(self, hidden_states, request=None):
+        h, normed = _attn_then_norm_2(self, hidden_states, request)
         return h + self.moe.forward(normed)
 
 
@@ -61,16 +65,8 @@ class LlamaLikeBlock(nn.Module):
         self.mlp = mlp.to(dev)
         self.device = dev
 
-    def forward(self, hidden_states):
-        norm_out = self.norm_1(hidden_states)
-        attn_output, _, _ = self.attn.forward(hidden_states=norm_out)
-        if (isinstance(self.norm_2, FasterTransformerRMSNorm) and attn_output.dtype == hidden_states.dtype == torch.float16
-                and attn_output.is_contiguous() and hidden_states.is_contiguous()):
-            h = attn_output  # becomes hidden_states + attn_output, in place in o_proj's own output buffer
-            normed = self.norm_2(hidden_states, residual=h)
-        else:
-            h = hidden_states.to(attn_output.device) + attn_output
-            normed = self.norm_2(h)
+    def forward(self, hidden_states, request=None):
+        h, normed = _attn_then_norm_2(self, hidden_states, request)
         return h + self.mlp.forward(normed)
 
     FOLD_NORMS_INTO_PROJECTIONS = True  # decode batches (rows <= 4), GEMM-layout qkv and gate|up
@@ -104,19 +100,19 @@ class LlamaLikeBlock(nn.Module):
                     for l in (a.qkv_proj, a.o_proj, m.down_proj)) and 2 * m.intermediate_size <= 131072
                 and a.qkv_proj.in_features <= 12288 and m.in_features <= 12288)
 
-    def _forward_stream_gemv(self, h):
+    def _forward_stream_gemv(self, h, request):
         B, S, H = h.shape
         q, o, d, n1, n2 = self.attn.qkv_proj, self.attn.o_proj, self.mlp.down_proj, self.norm_1, self.norm_2
         h0 = h.reshape(1, H)
         xqkv = ops.gemv_forward_ex(h0, q.qweight, q.scales, q.qzeros, q.group_size, norm_weight=n1.weight, norm_eps=n1.variance_epsilon)
-        heads, _, _ = self.attn.forward_qkv(xqkv.reshape(B, S, -1), apply_o_proj=False)
+        heads, _, _ = self.attn.forward_qkv(xqkv.reshape(B, S, -1), apply_o_proj=False, request=request)
         h1 = ops.gemv_forward_ex(heads.reshape(1, -1), o.qweight, o.scales, o.qzeros, o.group_size, add_residual=h0)
         pw, ps, pz = self.mlp.gate_up_pairs()
         act = ops.gemv_forward_ex(h1, pw, ps, pz, self.mlp.group_size, norm_weight=n2.weight, norm_eps=n2.variance_epsilon, silu_pairs=True)
         h2 = ops.gemv_forward_ex(act, d.qweight, d.scales, d.qzeros, d.group_size, add_residual=h1)
         return h2.reshape(B, S, H)
 
-    def forward_stream(self, x, h, ssq=None):
+    def forward_stream(self, x, h, ssq=None, request=None):
         """Residual stream kept by the caller (LlamaLikeModel): `h` is the stream, `x` a previous MLP output
         that has not been added yet (or None), `ssq` the per-tile sums of squares of `h` if the projection
         that produced it handed them over.  Decode batches run FIVE launches per block: qkv (norm folded
@@ -130,7 +126,7 @@ class LlamaLikeBlock(nn.Module):
 
             start = self.attn.start_pos
             try:
-                return None, self._forward_stream_gemv(h if x is None else h + x), None
+                return None, self._forward_stream_gemv(h if x is None else h + x, request), None
             except AwqHipError as e:  # a shape the row-streaming kernel does not take (K > 16384, group size < 128): separate launches
                 if getattr(e, "code", 0) != -3 or self.attn.start_pos != start:
                     raise
@@ -153,7 +149,7 @@ class LlamaLikeBlock(nn.Module):
 
             chain = isinstance(o, WQLinear_GEMM) and isinstance(d, WQLinear_GEMM) and self.mlp.activation is torch.nn.functional.silu
             if chain:
-                heads, _, _ = self.attn.forward_qkv(xqkv.reshape(B, S, -1), apply_o_proj=False)
+                heads, _, _ = self.attn.forward_qkv(xqkv.reshape(B, S, -1), apply_o_proj=False, request=request)
                 h1, ssq1 = ops.gemm_forward_ex(heads.reshape(B * S, -1), o.qweight, o.scales, o.qzeros, o.bias,
                                                add_residual=h.reshape(B * S, H), want_ssq=True)
                 qw, sc, qz = self.mlp._gate_up_fused()
@@ -161,13 +157,13 @@ class LlamaLikeBlock(nn.Module):
                 h2, ssq2 = ops.gemm_forward_ex(gate_up, d.qweight, d.scales, d.qzeros, d.bias, flags=ops.X_GATED_SILU,
                                                add_residual=h1, want_ssq=True)
                 return None, h2.reshape(B, S, H), ssq2
-            attn_output, _, _ = self.attn.forward_qkv(xqkv.reshape(B, S, -1))
+            attn_output, _, _ = self.attn.forward_qkv(xqkv.reshape(B, S, -1), request=request)
             qw, sc, qz = self.mlp._gate_up_fused()
             gate_up, hn = ops.gemm_forward_normed(attn_output.reshape(B * S, H), n2.weight, n2.variance_epsilon, qw, sc, qz,
                                                   residual=h.reshape(B * S, H))
             return self.mlp.forward(attn_output, gate_up=gate_up), hn.reshape(B, S, H), None
         norm_out = self.norm_1(h) if x is None else self.norm_1(x, residual=h)
-        attn_output, _, _ = self.attn.forward(hidden_states=norm_out)
+        attn_output, _, _ = self.attn.forward(hidden_states=norm_out, request=request)
         normed = self.norm_2(attn_output, residual=h)
         return self.mlp.forward(normed), h, None
 
@@ -200,8 +196,8 @@ class QwenBlock(nn.Module):
         self.mlp = mlp.to(dev)
         self.device = dev
 
-    def forward(self, hidden_states):
-        attn_output, _, _ = self.attn.forward(hidden_states=self.norm_1(hidden_states))
+    def forward(self, hidden_states, request=None):
+        attn_output, _, _ = self.attn.forward(hidden_states=self.norm_1(hidden_states), request=request)
         h = _add(hidden_states, attn_output)
         return h + self.mlp.forward(self.norm_2(h))
 
@@ -224,8 +220,8 @@ class Gemma2LikeBlock(nn.Module):
         self.norm_4 = norm_4.to(dev)
         self.device = dev
 
-    def forward(self, hidden_states):
-        attn_output, _, _ = self.attn.forward(hidden_states=self.norm_1(hidden_states))
+    def forward(self, hidden_states, request=None):
+        attn_output, _, _ = self.attn.forward(hidden_states=self.norm_1(hidden_states), request=request)
         h = _add(hidden_states, self.norm_2(attn_output))
         return h + self.norm_4(self.mlp(self.norm_3(h)))
 
@@ -247,8 +243,8 @@ class Phi3Block(nn.Module):
         self.mlp = mlp.to(dev)
         self.device = dev
 
-    def forward(self, hidden_states):
-        attn_output, _, _ = self.attn.forward(hidden_states=self.norm_1(hidden_states))
+    def forward(self, hidden_states, request=None):
+        attn_output, _, _ = self.attn.forward(hidden_states=self.norm_1(hidden_states), request=request)
         h = _add(hidden_states, attn_output)
         return h + self.mlp.forward(self.norm_2(h))
 
@@ -265,8 +261,8 @@ class MPTBlock(nn.Module):
         self.ffn = mpt_mlp.to(dev)
         self.device = dev
 
-    def forward(self, hidden_states):
-        attn_output, _, _ = self.attn.forward(hidden_states=self.norm_1(hidden_states))
+    def forward(self, hidden_states, request=None):
+        attn_output, _, _ = self.attn.forward(hidden_states=self.norm_1(hidden_states), request=request)
         h = _add(hidden_states, attn_output)
         return h + self.ffn.forward(self.norm_2(h))
 
@@ -297,10 +293,10 @@ class FalconDecoderLayer(nn.Module):
         self.mlp = mlp
         self.device = dev
 
-    def forward(self, hidden_states):
+    def forward(self, hidden_states, request=None):
         if self.new_decoder_arch:
             attn_in, mlp_in = self.ln_attn(hidden_states), self.ln_mlp(hidden_states)
         else:
             attn_in = mlp_in = self.input_layernorm(hidden_states)
-        attn_output, _, _ = self.attn.forward(hidden_states=attn_in)
+        attn_output, _, _ = self.attn.forward(hidden_states=attn_in, request=request)
         return _add(hidden_states, attn_output) + self.mlp.forward(mlp_in)

@@ -350,8 +350,7 @@ class GraphedDecoder:
         also moves its position words on by one, and they are restored from clones afterwards."""
         pos, ln = (self.pos_rows, self.len_rows) if rows else (self.pos, self.len)
         for b in self.blocks:
-            b.attn.use_device_positions(pos, ln, per_row=rows)
-            b.attn.decode_len_bound = bound
+            b.attn.use_device_positions(pos, ln, per_row=rows, bound=bound)
         keep = (pos.clone(), ln.clone()) if advance else None
         caller = torch.cuda.current_stream(self.device)  # (taken BEFORE entering the decoder's stream: the ids were copied on it)
         with torch.cuda.stream(self.stream):

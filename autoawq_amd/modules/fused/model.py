@@ -85,39 +85,26 @@ class LlamaLikeModel(nn.Module):
         device positions the caller has set on the blocks: no StepPlan -- nothing cached is forgotten, no id is sliced away --
         and neither `last_forward_num_tokens` nor the blocks' start_pos move; the caller advances its positions by what it
         accepts and restates the host bookkeeping (GraphedDecoder._sync_host_state).
-        extend=(pos_rows, count_rows, max_end): prefill at per-row positions (QuantAttentionFused._extend_qkv) -- [B, S] ids, row
-        b's first count_rows[b] at positions pos_rows[b] ..; the same bookkeeping rules as verify."""
-        if extend is not None:
-            for b in self.blocks:
-                b.attn.extend_rows = tuple(extend)
-            try:
-                return self._run_blocks(input_ids)
-            finally:
-                for b in self.blocks:
-                    b.attn.extend_rows = None
-        if verify:
-            for b in self.blocks:
-                b.attn.verify_rows = True
-            try:
-                return self._run_blocks(input_ids)
-            finally:
-                for b in self.blocks:
-                    b.attn.verify_rows = False
-        plan = StepPlan(input_ids, self.last_forward_num_tokens)
-        input_ids, self.last_forward_num_tokens = plan.input_ids, plan.tokens_seen
-        plan.apply(self.blocks)
-        return self._run_blocks(input_ids)
+        extend=(pos_rows, count_rows, max_end): prefill at per-row positions -- [B, S] ids, row b's first count_rows[b] at positions
+        pos_rows[b] ..; the same bookkeeping rules as verify.  Either is handed down to every block's attention as the call's
+        `request` (QuantAttentionFused._step): nothing is written onto a module, so an exception leaves nothing to undo."""
+        request = tuple(extend) if extend is not None else "verify" if verify else None
+        if request is None:
+            plan = StepPlan(input_ids, self.last_forward_num_tokens)
+            input_ids, self.last_forward_num_tokens = plan.input_ids, plan.tokens_seen
+            plan.apply(self.blocks)
+        return self._run_blocks(input_ids, request)
 
-    def _run_blocks(self, input_ids):
+    def _run_blocks(self, input_ids, request=None):
         h = self.embedding(input_ids)
         if self._stream_mode(h):
             x, ssq = None, None
             for layer in self.blocks:  # residual adds and norms ride on the projections (block.forward_stream)
-                x, h, ssq = layer.forward_stream(x, h, ssq)
+                x, h, ssq = layer.forward_stream(x, h, ssq, request)
             h = self.norm(x, residual=h) if x is not None else self.norm(h)
         else:
             for layer in self.blocks:
-                h = layer(h)
+                h = layer(h, request=request)
             h = self.norm(h)
         try:
             from transformers.modeling_outputs import BaseModelOutputWithPast
