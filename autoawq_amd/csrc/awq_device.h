@@ -61,6 +61,21 @@ AWQ_DEV float awq_silu_mul_f32(float g, float u) {
     return r;
 }
 
+// RoPE, one output of a pair: p c + q s in fp32, for the caller to convert to fp16.  With (a, b) = dims (i, i + rot / 2) of a head
+// and (c, s) the cosine and sine of the position's angle, dim i gets a c - b s = awq_rope_term(a, b, c, -s) and dim i + rot / 2 gets
+// a s + b c = awq_rope_term(b, a, c, s): the output's OWN dim meets the cosine.  ONE definition for rope_kv_append_body and for the
+// FUSED rotation of awq_decode_attn_kernel (decoder.hip), whose appended cache rows must have the same bits.  The fma is written out
+// -- the product with the cosine rounded to fp32 on its own, the product with the sine exact inside the fma -- contraction is off, and
+// the fp32 result is pinned in a register before the conversion.  Left to the compiler, the append kernel fused the OTHER product of
+// a c - b s and converted straight from the fma (v_fma_mixlo_f16: one rounding) where the fused step rounded to fp32 first: on rows
+// built to cancel (a c ~ b s) the two cache rows differed in dozens of elements (tests/test_gpu_rope_bounds.py).
+AWQ_DEV float awq_rope_term(float p, float q, float c, float s) {
+#pragma clang fp contract(off)
+    float r = __builtin_fmaf(q, s, p * c);
+    asm("" : "+v"(r));
+    return r;
+}
+
 // half2(1024 + column 2J, 1024 + column 2J+1) of one packed word
 template <int J>
 AWQ_DEV uint32_t awq_pair_magic(uint32_t q) {

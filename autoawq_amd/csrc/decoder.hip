@@ -210,8 +210,8 @@ AWQ_DEV void rope_kv_append_body(const half_t* qkv, half_t* q_out, CacheT* k_cac
     if (slot < Hq + Hkv && i < half_rot) {
         const float c = cos_t[(int64_t)pos * half_rot + i], sn = sin_t[(int64_t)pos * half_rot + i];
         const float a = (float)src[i], bb = (float)src[i + half_rot];
-        dst[i] = (half_t)(a * c - bb * sn);
-        dst[i + half_rot] = (half_t)(a * sn + bb * c);
+        dst[i] = (half_t)awq_rope_term(a, bb, c, -sn);
+        dst[i + half_rot] = (half_t)awq_rope_term(bb, a, c, sn);
     } else if (slot < Hq + Hkv) {  // pass-through part of a partially rotated head: dims rot .. D-1
         const int d0 = rot + 2 * (i - half_rot);
         if (d0 < D) dst[d0] = src[d0];
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(64) void awq_rope_kv_append_n_fp8_kernel(const half
 // rotated k and its v straight from that row -- cache row `pos` is not read by anybody in this
 // launch -- and the one block whose chunk holds `pos` appends them to the caches.  len_dev then
 // holds the POSITION (length - 1).  Same roundings as awq_rope_kv_append followed by the plain
-// kernel: rotated values pass through fp16.
+// kernel: one rotation for both (awq_rope_term, awq_device.h), rotated values pass through fp16.
 // EXTRA (plain form only): logit soft-capping s := cap * tanh(s / cap) (attn.py:150,166 `softcap=`) and ALiBi, a per-head linear
 // bias slope_h * (t - pos) on the key position (attn.py:89-125,149,165 `alibi_slopes=`), in that order like flash-attn.
 // ROWS (the *_rows entry points): len_dev is [B], sequence b reads its own length (FUSED: position) from len_dev[b].  The launch
@@ -376,13 +376,14 @@ __global__ __launch_bounds__(256) void awq_decode_attn_kernel(const half_t* __re
             const int i = (8 * c + e) & 63;
             cs[e] = cos_t[(int64_t)pos * 64 + i];
             sn[e] = sin_t[(int64_t)pos * 64 + i];
+            if (c < 8) sn[e] = -sn[e];  // lanes c < 8 hold dims d < 64: a c - b s; the others b c + a s (awq_rope_term)
         }
         auto rotate = [&](half8_t x) -> half8_t {
             half8_t o;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float mine = (float)x[e], other = AWQ_ATTN_NO_DPP ? __shfl_xor(mine, 8, 64) : dpp_f<0x128>(mine);  // row_ror:8 = lane c ^ 8 of the row: dims d and d +- 64
-                o[e] = (c < 8) ? (half_t)(mine * cs[e] - other * sn[e]) : (half_t)(other * sn[e] + mine * cs[e]);
+                o[e] = (half_t)awq_rope_term(mine, other, cs[e], sn[e]);
             }
             return o;
         };

@@ -53,6 +53,8 @@ n_out: the scale multiply and every addition of folded values down to the fp32 v
         rounding of the exact value) as ITS activations; slack_k = the larger distance from |x16_k| to those two ends (0 unless
         xn_k lies within e of a rounding boundary).  The plain bound is then taken at |x| + slack, with
         D = sum_k slack_k |W_k| added to sum_f |s_f d_f| and (1 + 2^-10) D to the bound (the moved product and its ulp).
+        gemv_mfma's NORM staging (awq_gemm_forward_normed / _ex, gemv_mfma.hip:254-308) takes the same extension with its own e:
+        norm_prologue(..., depth) with the depths tests/norm_rope_bound.py counts (its statistic pass, or the producer's ssq_out).
   gemv_nk (autoawq_amd/csrc/gemv_nk.hip; biases 1024 / 64, :62-68), gemv_lds (autoawq_amd/csrc/gemv_lds.hip; 1024 / 64, :144-147),
   gemv_mfma (autoawq_amd/csrc/gemv_mfma.hip; bias 16, :15-16, :104), gemv_fast (autoawq_amd/csrc/gemv_fast.hip; bias 16, :59) and the GEMVFast form of
   gemv_batch (autoawq_amd/csrc/gemv_batch.hip:143, :447-448; bias 16)
@@ -225,13 +227,13 @@ def _fold_sums(case, layout, fold):
 def bound(case, layout, kernel, n_out=None, out_scale=None, residual=None, x_slack=None, n_p=None):
     """(want, bound) [M, N] float64 for `kernel`'s arithmetic class.  n_out, n_p: the launch's own depths where the caller knows them;
     out_scale [M]: FX_SCALE's per-row fp32 factor of the fp32 sum; residual [M, N]: FX_RES's second rounding; x_slack [M, K]:
-    how far the kernel's own activations may lie from case.x (FX_NORM, norm_prologue)."""
+    how far the kernel's own activations may lie from case.x (FX_NORM / gemv_mfma's NORM staging, norm_prologue)."""
     M, K, N = case.shape
     g = case.g
     ax = np.abs(case.x.astype(np.float64))
     moved = 0.0
     if x_slack is not None:
-        assert kernel.startswith("gemv_rows")
+        assert kernel in FACTORISED  # (a norm prologue: gemv_rows' FX_NORM, gemv_mfma's NORM staging)
         ax = ax + x_slack
         moved = x_slack @ np.abs(weights_exact(case, layout))
     if kernel in REF_WEIGHT:
@@ -275,15 +277,16 @@ SILU_SLOPE = 1.1   # max |silu'| = 1.0998 (at x = 2.3994)
 SILU_N = 16        # awq_silu_mul_f32's four fp32 operations
 
 
-def norm_prologue(x, norm_weight, eps):
-    """FX_NORM: (x16 [M, K] float16 = fp16 of the exactly normalised activations, slack [M, K] float64)"""
-    x64 = x.astype(np.float64)
-    inv = 1.0 / np.sqrt((x64 ** 2).mean(1, keepdims=True) + float(np.float32(eps)))
-    xn = x64 * inv * norm_weight.astype(np.float64)[None]
-    a, e = np.abs(xn), 1.01 * gamma(NORM_N)
-    mid = a.astype(np.float16).astype(np.float64)  # (numpy rounds float64 to float16 once, to nearest even)
-    lo, hi = (a * (1.0 - e)).astype(np.float16).astype(np.float64), (a * (1.0 + e)).astype(np.float16).astype(np.float64)
-    return (np.sign(xn) * mid).astype(np.float16), np.maximum(hi - mid, mid - lo)
+def norm_prologue(x, norm_weight, eps, depth=NORM_N):
+    """A norm folded into a matmul: (x16 [M, K] float16 = fp16 of the exactly normalised activations, slack [M, K] float64) for an
+    implementation whose statistic has `depth` roundings (tests/norm_rope_bound.py counts them; FX_NORM of gemv_rows: NORM_N)"""
+    import norm_rope_bound as nrb
+
+    xn = nrb.norm_reference(x, norm_weight, eps)
+    lo, hi = nrb.norm_window(xn, depth)
+    x16 = xn.astype(np.float16)  # (numpy rounds float64 to float16 once, to nearest even)
+    mid = x16.astype(np.float64)
+    return x16, np.maximum(hi - mid, mid - lo)
 
 
 def silu(v):

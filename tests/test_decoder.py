@@ -13,6 +13,8 @@ import pytest
 import torch
 
 import attn_bound
+import matmul_bound as mb
+import norm_rope_bound as nrb
 from conftest import GOLDEN, golden
 from test_checkpoint import ckpt, skeleton
 
@@ -202,22 +204,27 @@ def ops():
 @pytest.mark.gpu
 @pytest.mark.parametrize("M,H", [(1, 4096), (3, 256), (17, 5120), (2, 8192), (4, 136)])
 def test_rmsnorm_vs_oracle(ops, M, H):
+    """the derived window of tests/norm_rope_bound.py around the float64 reference (at most two neighbouring fp16 values, the
+    oracle's among them: never wider than the one-ulp check it replaces)"""
     from oracle import decoder_oracle
 
     gen = torch.Generator().manual_seed(M * 1000 + H)
     x = (torch.randn((M, H), generator=gen) * 2).half()
     w = (torch.rand(H, generator=gen) + 0.5).half()
-    want = decoder_oracle.rmsnorm_reference(x.numpy(), w.numpy(), 1e-5).astype(np.float64)
-    got = ops.rmsnorm(x.cuda(), w.cuda(), 1e-5).cpu().numpy().astype(np.float64)
-    assert (np.abs(got - want) <= ulp16(want)).all()
+    lo, hi = nrb.norm_window(nrb.norm_reference(x.numpy(), w.numpy(), 1e-5), nrb.depth_rmsnorm(H))
+    nrb.assert_in_window(decoder_oracle.rmsnorm_reference(x.numpy(), w.numpy(), 1e-5), lo, hi, "the oracle")
+    assert (hi - lo <= ulp16(lo)).all()
+    got = ops.rmsnorm(x.cuda(), w.cuda(), 1e-5).cpu().numpy()
+    nrb.assert_in_window(got, lo, hi, f"rmsnorm M{M} H{H}")
     # residual form: r <- fp16(r + x) bit for bit, and the norm of that
     r = torch.randn((M, H), generator=gen).half()
     rd = r.cuda()
-    got2 = ops.rmsnorm(x.cuda(), w.cuda(), 1e-5, residual=rd).cpu().numpy().astype(np.float64)
+    got2 = ops.rmsnorm(x.cuda(), w.cuda(), 1e-5, residual=rd).cpu().numpy()
     rsum = (x.float() + r.float()).half()
     assert torch.equal(rd.cpu(), rsum)
-    want2 = decoder_oracle.rmsnorm_reference(rsum.numpy(), w.numpy(), 1e-5).astype(np.float64)
-    assert (np.abs(got2 - want2) <= ulp16(want2)).all()
+    y2, h2 = nrb.norm_reference(x.numpy(), w.numpy(), 1e-5, r.numpy())
+    assert np.array_equal(h2, rsum.numpy())
+    nrb.assert_in_window(got2, *nrb.norm_window(y2, nrb.depth_rmsnorm(H)), f"rmsnorm + residual M{M} H{H}")
 
 
 @pytest.mark.gpu
@@ -484,12 +491,26 @@ def test_fused_rope_append_attention_equals_the_two_kernels(ops, B, Hq, Hkv, pos
         assert (got.float() - want.float()).abs().max() <= 2e-3 * want.float().abs().max() + 2 ** -11
 
 
+def derived_normed_bound(ops, got, h16, norm_w, eps, depth, qweight, qzeros, scales, what, g=128):
+    """`got` [M, N] of a projection with a folded norm against matmul_bound's gemv_mfma bound, the activations fp16 of the exact
+    norm of h16 with the window of `depth` as slack -- on the first and the last 128 columns (the bound is per element)"""
+    N = got.shape[1]
+    for c0 in sorted({0, N - 128}):
+        wi = ops.unpack_int4(qweight[:, c0 // 8:(c0 + 128) // 8].contiguous().cuda()).cpu().numpy().astype(np.uint8)
+        zi = ops.unpack_int4(qzeros[:, c0 // 8:(c0 + 128) // 8].contiguous().cuda()).cpu().numpy().astype(np.uint8)
+        x16, slack = mb.norm_prologue(h16, norm_w.cpu().numpy(), eps, depth)
+        want, bnd = mb.bound(mb.Case(x16, wi, zi, scales[:, c0:c0 + 128].numpy(), g), "gemm", "gemv_mfma", x_slack=slack)
+        mb.assert_within(got[:, c0:c0 + 128].cpu().numpy(), want, bnd, f"{what} columns {c0}..{c0 + 127}")
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("M", [1, 2, 4])
 @pytest.mark.parametrize("K,N", [(4096, 12288), (512, 256), (11008, 4096)])
 def test_norm_folded_into_projection(ops, M, K, N):
     """awq_gemm_forward_normed == awq_rmsnorm_forward (with residual add) + awq_gemm_forward: the residual
-    stream bit for bit, the product to the kernel tolerance (the sum of squares is reduced in another order)."""
+    stream bit for bit, the product to the kernel tolerance (the sum of squares is reduced in another order) -- and, on the
+    first and last 128 columns, within the bound derived from the kernel's own arithmetic around the float64 product
+    (tests/matmul_bound.py with the norm's window as slack, tests/norm_rope_bound.py)."""
     from test_gpu_parity import fullrange_case
 
     qw, qz, s, _, _ = fullrange_case(K, N, 128, 1, seed=K + M, realistic=True)
@@ -510,6 +531,10 @@ def test_norm_folded_into_projection(ops, M, K, N):
             assert torch.equal(stream, r2) and torch.equal(residual, res)  # the input stream is not written
         err = (got.float() - want).abs()
         assert float(err.max()) <= 2e-3 * float(want.abs().max()) + 1e-3, float(err.max())
+        h16 = (x if residual is None else stream).cpu().numpy()
+        if residual is not None:
+            assert np.array_equal(h16, nrb.stream_sum(x.cpu().numpy(), res.cpu().numpy()))
+        derived_normed_bound(ops, got, h16, w, 1e-5, nrb.depth_mfma_norm(K), qw, qz, s, f"M{M} K{K} N{N}")
     with pytest.raises(Exception):
         ops.gemm_forward_normed(torch.zeros((5, K), dtype=torch.float16, device="cuda"), w, 1e-5, dq, ds, dz)
 
@@ -521,7 +546,9 @@ def test_residual_epilogue_hands_the_statistic_to_the_next_projection(ops, M, H,
     """awq_gemm_forward_ex: a row-parallel projection (o_proj / down) adds the residual stream in its
     epilogue and emits per-tile sums of squares; the next projection normalises from them without a
     statistic pass.  Stream: bit-identical to `h + proj(x)` in torch (two fp16 roundings); the partial
-    sums match the stored values; the normed product matches rmsnorm + gemm within the kernel tolerance."""
+    sums match the stored values; the normed product matches rmsnorm + gemm within the kernel tolerance.  Beside the
+    kernel-to-kernel comparison: each tile's partial within gamma(depth) of the float64 sum of squares of the returned stream
+    and the normed product within the derived bound (tests/norm_rope_bound.py, tests/matmul_bound.py)."""
     from test_gpu_parity import fullrange_case
 
     qw1, qz1, s1, _, _ = fullrange_case(I, H, 128, 1, seed=H + M, realistic=True)      # down: I -> H
@@ -543,10 +570,13 @@ def test_residual_epilogue_hands_the_statistic_to_the_next_projection(ops, M, H,
     assert ssq.shape == (M, tiles)
     want_ssq = (stream.float() ** 2).reshape(M, tiles, -1).sum(-1)
     assert torch.allclose(ssq, want_ssq, rtol=1e-5, atol=1e-6)
+    want64 = nrb.ssq_tiles_reference(stream.cpu().numpy())
+    assert (np.abs(ssq.cpu().numpy().astype(np.float64) - want64) <= nrb.gamma(nrb.SSQ_TILE_N) * want64).all()
     nxt, none = ops.gemm_forward_ex(stream, *d2, norm_weight=w, norm_eps=1e-5, ssq_in=ssq)
     assert none is None
     err = (nxt.float() - next_ref).abs()
     assert float(err.max()) <= 2e-3 * float(next_ref.abs().max()) + 1e-3, float(err.max())
+    derived_normed_bound(ops, nxt, stream.cpu().numpy(), w, 1e-5, nrb.depth_mfma_ssq(), qw2, qz2, s2, f"M{M} H{H} I{I}")
     assert ops.workspace_is_clean(h.device)
 
 
