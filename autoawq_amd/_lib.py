@@ -65,6 +65,15 @@ class AwqSampleRowsArgs(ctypes.Structure):
                                          ("max_new", c_void_p)]
 
 
+class AwqSampleSlotsArgs(ctypes.Structure):
+    """struct AwqSampleSlotsArgs of include/awq_hip.h (same field order): the sampler over the B x T slots of a verify step."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("logits", c_void_p), ("B", c_int64), ("T", c_int64),
+                ("V", c_int64), ("row_stride", c_int64), ("params", c_void_p), ("cnt", c_void_p), ("tok", c_void_p),
+                ("pred", c_void_p), ("finished", c_void_p), ("status", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", c_size_t), ("stream", c_void_p), ("proc", c_void_p), ("history", c_void_p),
+                ("history_stride", c_int64)]
+
+
 class AwqSpecParams(ctypes.Structure):
     """struct AwqSpecParams of include/awq_hip.h (same field order; lives in device memory)."""
     _fields_ = [("n_eos", ctypes.c_int32), ("pad", ctypes.c_int32), ("max_new_tokens", ctypes.c_int32),
@@ -77,6 +86,12 @@ class AwqSpecArgs(ctypes.Structure):
                 ("tok", c_void_p), ("pred", c_void_p), ("hist", c_void_p), ("hist_cap", c_int64), ("n_hist", c_void_p),
                 ("cnt", c_void_p), ("ring", c_void_p), ("ring_cap", c_int64), ("finished", c_void_p), ("pos_rows", c_void_p),
                 ("len_rows", c_void_p), ("status", c_void_p), ("steps", c_void_p), ("stream", c_void_p)]
+
+
+class AwqSpecHistoryArgs(ctypes.Structure):
+    """struct AwqSpecHistoryArgs of include/awq_hip.h (same field order)."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("history", c_void_p), ("history_stride", c_int64),
+                ("V", c_int64)]
 
 
 class AwqLogprobArgs(ctypes.Structure):
@@ -164,6 +179,7 @@ SIGNATURES = {
     "awq_sample_tokens_ex": (c_int, [ctypes.POINTER(AwqSampleArgs), ctypes.POINTER(AwqSampleProcArgs)]),
     "awq_sample_history_seed": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),
     "awq_sample_tokens_rows": (c_int, [ctypes.POINTER(AwqSampleRowsArgs)]),
+    "awq_sample_tokens_slots": (c_int, [ctypes.POINTER(AwqSampleSlotsArgs)]),
     "awq_verify_attention_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "awq_verify_attention_splits": (c_int, [c_int64] * 5),
     "awq_verify_attention_rows": (c_int, [c_void_p] * 5 + [c_int64] * 7 + [c_float, c_void_p, c_size_t, c_void_p]),
@@ -172,6 +188,7 @@ SIGNATURES = {
     "awq_prefill_attention_rows": (c_int, [c_void_p] * 6 + [c_int64] * 7 + [c_float, c_float, c_void_p, c_void_p]),
     "awq_spec_accept": (c_int, [ctypes.POINTER(AwqSpecArgs)]),
     "awq_ngram_draft": (c_int, [ctypes.POINTER(AwqSpecArgs)]),
+    "awq_spec_accept_ex": (c_int, [ctypes.POINTER(AwqSpecArgs), ctypes.POINTER(AwqSpecHistoryArgs)]),
     "awq_token_logprobs": (c_int, [ctypes.POINTER(AwqLogprobArgs)]),
 }
 

@@ -59,6 +59,18 @@
 // not touched.  max_new (optional): with max_new[r] > 0 the row latches finished[r] in the launch that emits token index
 // t[r] >= max_new[r]; that token is real, the following ones are pad.
 // The ROWS = false instantiations are the kernels they were before the flag (DESIGN.md 3.10 states the comparison).
+//
+// Slots form (awq_sample_tokens_slots, the SLOTS template flag; pinned by tests/test_spec_sampling_cpu.py and
+// tests/test_gpu_spec_sampling_kernels.py): the sampler of a speculative verify step.  The launch has B * T logits rows; row
+// r = b * T + j is slot j of request b (grid = chunks x T x B, so a block reads b and j from its block index).  Slot (b, j) answers
+// "which token would the rows form emit for request b at token index cnt[b] + 1 + j, given the drafts tok[b, 1 .. j] before it":
+// it reads params[b] and (PROC) proc[b], the Philox counter is (cnt[b] + 1 + j, b, i / 4, 0), EOS ids are suppressed while
+// cnt[b] + 1 + j <= min_new_tokens[b], and the penalty covers history row b OR the bits of tok[b, 1 .. j] (process8 compares the
+// <= 7 draft ids, block-uniform loads, with the 8 indices of the thread: no second bitmap; ids outside [0, V) match nothing).
+// It writes pred[r] and the status bit r and NOTHING else: cnt, history, tok and finished are read only, there is no ring, no
+// latch and no launch-wide step (awq_spec_accept owns them).  A slot of a finished request emits pad and sets no bit.  Every pass
+// and combine is the one above on the same arithmetic, so slot (b, j) equals row b of the rows form at that token index and
+// history bit for bit (contract E1).  The SLOTS = false instantiations are the kernels they were before the flag.
 #include "awq_device.h"
 #include "awq_internal.h"
 
@@ -135,13 +147,41 @@ struct RowsCtx : Ctx {
 struct RowsProcCtx : ProcCtx {
     const int32_t* max_new;
 };
-template <bool PROC, bool ROWS = false>
-using CtxT = typename std::conditional<ROWS, typename std::conditional<PROC, RowsProcCtx, RowsCtx>::type,
-                                       typename std::conditional<PROC, ProcCtx, Ctx>::type>::type;
+// The slots form (SLOTS = true): params and proc point at [B] arrays, cnt [B] and tok [B, T] replace t, Ctx::B is the launch's
+// B * T rows, Ctx::t is not used; types of their own, so that the SLOTS = false kernels keep their argument layouts.
+struct SlotsCtx : Ctx {
+    const int32_t* cnt;
+    const int64_t* tok;
+};
+struct SlotsProcCtx : ProcCtx {
+    const int32_t* cnt;
+    const int64_t* tok;
+};
+template <bool PROC, bool ROWS = false, bool SLOTS = false>
+using CtxT = typename std::conditional<
+    SLOTS, typename std::conditional<PROC, SlotsProcCtx, SlotsCtx>::type,
+    typename std::conditional<ROWS, typename std::conditional<PROC, RowsProcCtx, RowsCtx>::type,
+                              typename std::conditional<PROC, ProcCtx, Ctx>::type>::type>::type;
 
 // The parameters, token index and processors of a row: element `row` in the rows form, the one shared struct / word otherwise.
 // (An index that folds to 0 in the front end: accessor functions returning references changed the schedule of the ROWS = false pass 3.)
 #define AWQ_ROW_OF(ROWS, row) ((ROWS) ? (row) : 0)
+
+// What a block works on.  row: the launch row (logits, workspace, out, status bit).  par: the element of params / proc / t it
+// reads.  own: the request's row of finished / history, and the row word of its Philox counter.  slot: its slot in the request.
+// Outside the slots form row == own and slot == 0; in the slots form (grid chunks x T x B) row = b * T + j, par = own = b, slot = j.
+struct RowId {
+    int row, par, own, slot;
+};
+template <bool ROWS, bool SLOTS> AWQ_DEV RowId row_id() {
+    if constexpr (SLOTS) {
+        const int b = blockIdx.z, j = blockIdx.y;
+        return RowId{b * (int)gridDim.y + j, b, b, j};
+    } else {
+        const int row = blockIdx.y;
+        return RowId{row, AWQ_ROW_OF(ROWS, row), row, 0};
+    }
+}
 
 AWQ_DEV WsHead* head_of(const Ctx& c) { return reinterpret_cast<WsHead*>(c.ws); }
 AWQ_DEV RowWs* row_of(const Ctx& c, int r) { return reinterpret_cast<RowWs*>(c.ws + kHeadBytes + (size_t)r * kRowBytes); }
@@ -151,6 +191,13 @@ template <typename T> AWQ_DEV T ld(const T* p) { return __hip_atomic_load(p, __A
 template <typename T> AWQ_DEV void st(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 template <typename T> AWQ_DEV void add(T* p, T v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 AWQ_DEV void amax(unsigned long long* p, unsigned long long v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// the 1-based index of the token the block selects, read at block start: the t word, or in the slots form cnt[b] + 1 + j
+template <bool ROWS, bool SLOTS, typename C> AWQ_DEV int32_t token_index(const C& c, const RowId& id) {
+    if constexpr (SLOTS)
+        return ld(c.cnt + id.par) + 1 + id.slot;
+    else
+        return ld(c.t + id.par);
+}
 
 // fp16 bits -> monotone key (larger key = larger value; -0 == +0)
 AWQ_DEV uint32_t key16(uint32_t b) {
@@ -233,8 +280,10 @@ AWQ_DEV void load8(const Ctx& c, int row, int i0, uint32_t h[8]) {
 
 // The processors (PROC) on the 8 logits of this thread.  eos_on: t <= min_new_tokens (block-uniform).  The history bits of
 // i0 .. i0 + 7 are one byte (i0 % 8 == 0): bit v % 8 of byte v / 8 is bit v % 32 of word v / 32 (little endian).
-template <bool ROWS>
-AWQ_DEV void process8(const ProcCtx& c, const AwqSampleParams& P, int row, int i0, bool eos_on, uint32_t h[8]) {
+// SLOTS: the history row is the request's, and the drafts in front of the slot, tok[b, 1 .. j], count as seen.
+template <bool ROWS, bool SLOTS>
+AWQ_DEV void process8(const CtxT<true, ROWS, SLOTS>& c, const AwqSampleParams& P, const RowId& id, int i0, bool eos_on,
+                      uint32_t h[8]) {
     if (eos_on) {
         const int n = P.n_eos < 8 ? P.n_eos : 8;
         for (int e = 0; e < n; ++e) {
@@ -244,9 +293,16 @@ AWQ_DEV void process8(const ProcCtx& c, const AwqSampleParams& P, int row, int i
                 if (d == j) h[j] = 0xFC00u;
         }
     }
-    const float p = c.proc[AWQ_ROW_OF(ROWS, row)].repetition_penalty;
+    const float p = c.proc[id.par].repetition_penalty;
     if (p == 1.f || i0 >= c.V) return;  // (p = 1: v * 1 and v / 1 are v, and fp16(float(h)) is h)
-    const uint32_t bits = reinterpret_cast<const uint8_t*>(c.history + (int64_t)row * c.history_stride)[i0 >> 3];
+    uint32_t bits = reinterpret_cast<const uint8_t*>(c.history + (int64_t)id.own * c.history_stride)[i0 >> 3];
+    if constexpr (SLOTS) {
+        const int64_t* in = c.tok + (int64_t)id.own * (int)gridDim.y;
+        for (int k = 1; k <= id.slot; ++k) {  // (at most 7, block-uniform)
+            const int64_t d = in[k];
+            if (d >= i0 && d < i0 + 8 && d < c.V) bits |= 1u << (int)(d - i0);
+        }
+    }
     if (!bits) return;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -259,8 +315,8 @@ AWQ_DEV void process8(const ProcCtx& c, const AwqSampleParams& P, int row, int i
 }
 
 // t <= min_new_tokens, read at block start
-template <bool ROWS> AWQ_DEV bool eos_suppressed(const ProcCtx& c, int row) {
-    return ld(c.t + AWQ_ROW_OF(ROWS, row)) <= c.proc[AWQ_ROW_OF(ROWS, row)].min_new_tokens;
+template <bool ROWS, bool SLOTS> AWQ_DEV bool eos_suppressed(const CtxT<true, ROWS, SLOTS>& c, const RowId& id) {
+    return token_index<ROWS, SLOTS>(c, id) <= c.proc[id.par].min_new_tokens;
 }
 
 AWQ_DEV bool is_greedy(const AwqSampleParams& P, int forced) { return forced || P.do_sample == 0 || !(P.temperature > 0.f); }
@@ -298,11 +354,16 @@ AWQ_DEV void set_status(const Ctx& c, int row) {
 // its load drained, before this row's add, and only the last add's row writes t.
 // ROWS: t is the row's own word t[row]; every block of the row has read it before arriving on the row counter, so this block (the
 // row's last) advances it here, and the launch counter is not used.  max_new: the row's budget latch.
-template <bool PROC, bool ROWS>
-AWQ_DEV void finish_row(const CtxT<PROC, ROWS>& c, int row, const AwqSampleParams& P, int64_t tok, bool sampled) {
+// SLOTS: the slot's token goes to out[row] and that is all -- no t, ring, finished or history word moves (awq_spec_accept's).
+template <bool PROC, bool ROWS, bool SLOTS>
+AWQ_DEV void finish_row(const CtxT<PROC, ROWS, SLOTS>& c, int row, const AwqSampleParams& P, int64_t tok, bool sampled) {
     RowWs* w = row_of(c, row);
     const RowState zero{};
     w->st = zero;
+    if constexpr (SLOTS) {
+        c.out[row] = tok;
+        return;
+    }
     const int32_t t = ld(c.t + AWQ_ROW_OF(ROWS, row));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     c.out[row * c.out_stride] = tok;
@@ -370,15 +431,16 @@ AWQ_DEV uint32_t find_from_top(Get get, unsigned long long base, Ok ok, unsigned
 }
 
 // ---- pass 1 ----------------------------------------------------------------------------------------------------------
-template <bool PROC, bool ROWS>
-__global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC, ROWS> c, int greedy_forced) {
-    const int row = blockIdx.y, tid = threadIdx.x;
-    const AwqSampleParams& P = c.params[AWQ_ROW_OF(ROWS, row)];  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
+template <bool PROC, bool ROWS, bool SLOTS>
+__global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC, ROWS, SLOTS> c, int greedy_forced) {
+    const RowId id = row_id<ROWS, SLOTS>();
+    const int row = id.row, tid = threadIdx.x;
+    const AwqSampleParams& P = c.params[id.par];  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
     const bool greedy = is_greedy(P, greedy_forced);
     bool eos_on = false;
-    if constexpr (PROC) eos_on = eos_suppressed<ROWS>(c, row);
+    if constexpr (PROC) eos_on = eos_suppressed<ROWS, SLOTS>(c, id);
     RowWs* w = row_of(c, row);
-    const bool fin = c.finished && c.finished[row] != 0;
+    const bool fin = c.finished && c.finished[id.own] != 0;
     __shared__ uint32_t s_cnt[256];
     __shared__ unsigned long long s_best[kThreads / 64];
     __shared__ uint32_t s_bad;
@@ -389,7 +451,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC, ROWS> c, int
         const int i0 = blockIdx.x * kChunk + tid * kPerThread;
         uint32_t h[8];
         load8(c, row, i0, h);
-        if constexpr (PROC) process8<ROWS>(c, P, row, i0, eos_on, h);
+        if constexpr (PROC) process8<ROWS, SLOTS>(c, P, id, i0, eos_on, h);
         unsigned long long best = 0;
         uint32_t bad = 0;
 #pragma unroll
@@ -436,7 +498,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC, ROWS> c, int
     const bool live = !fin && !bad && best != 0;
     if (!fin && !live && tid == 0) set_status(c, row);
     if (greedy) {
-        if (tid == 0) finish_row<PROC, ROWS>(c, row, P, live ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, live);
+        if (tid == 0) finish_row<PROC, ROWS, SLOTS>(c, row, P, live ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, live);
         return;
     }
     __shared__ uint32_t s_hist[256];
@@ -464,13 +526,14 @@ __global__ __launch_bounds__(kThreads) void sample_pass1(CtxT<PROC, ROWS> c, int
 }
 
 // ---- pass 2 ----------------------------------------------------------------------------------------------------------
-template <bool PROC, bool ROWS>
-__global__ __launch_bounds__(kThreads) void sample_pass2(CtxT<PROC, ROWS> c, int greedy_forced) {
-    const int row = blockIdx.y, tid = threadIdx.x;
-    const AwqSampleParams& P = c.params[AWQ_ROW_OF(ROWS, row)];  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
+template <bool PROC, bool ROWS, bool SLOTS>
+__global__ __launch_bounds__(kThreads) void sample_pass2(CtxT<PROC, ROWS, SLOTS> c, int greedy_forced) {
+    const RowId id = row_id<ROWS, SLOTS>();
+    const int row = id.row, tid = threadIdx.x;
+    const AwqSampleParams& P = c.params[id.par];  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
     if (is_greedy(P, greedy_forced)) return;
     bool eos_on = false;
-    if constexpr (PROC) eos_on = eos_suppressed<ROWS>(c, row);
+    if constexpr (PROC) eos_on = eos_suppressed<ROWS, SLOTS>(c, id);
     RowWs* w = row_of(c, row);
     const RowState S = w->st;
     const bool topp = P.top_p < 1.f;
@@ -486,7 +549,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass2(CtxT<PROC, ROWS> c, int
         const int i0 = blockIdx.x * kChunk + tid * kPerThread;
         uint32_t h[8];
         load8(c, row, i0, h);
-        if constexpr (PROC) process8<ROWS>(c, P, row, i0, eos_on, h);
+        if constexpr (PROC) process8<ROWS, SLOTS>(c, P, id, i0, eos_on, h);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             if ((h[j] & 0x7FFFu) >= 0x7C00u) continue;
@@ -554,13 +617,14 @@ __global__ __launch_bounds__(kThreads) void sample_pass2(CtxT<PROC, ROWS> c, int
 }
 
 // ---- pass 3 ----------------------------------------------------------------------------------------------------------
-template <bool PROC, bool ROWS>
-__global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC, ROWS> c, int greedy_forced) {
-    const int row = blockIdx.y, tid = threadIdx.x;
-    const AwqSampleParams& P = c.params[AWQ_ROW_OF(ROWS, row)];  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
+template <bool PROC, bool ROWS, bool SLOTS>
+__global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC, ROWS, SLOTS> c, int greedy_forced) {
+    const RowId id = row_id<ROWS, SLOTS>();
+    const int row = id.row, tid = threadIdx.x;
+    const AwqSampleParams& P = c.params[id.par];  // (a by-value copy is promoted to 16 KB of LDS / spilled to scratch)
     if (is_greedy(P, greedy_forced)) return;
     bool eos_on = false;
-    if constexpr (PROC) eos_on = eos_suppressed<ROWS>(c, row);
+    if constexpr (PROC) eos_on = eos_suppressed<ROWS, SLOTS>(c, id);
     RowWs* w = row_of(c, row);
     const RowState S = w->st;
     const bool topp = S.bin_p != kNone && P.top_p < 1.f;
@@ -570,11 +634,11 @@ __global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC, ROWS> c, int
     __syncthreads();
     if (S.mode == MODE_LIVE) {
         const float mx = key_to_float(S.maxkey), T = P.temperature;
-        const unsigned long long seed = P.seed, t = (unsigned long long)ld(c.t + AWQ_ROW_OF(ROWS, row));
+        const unsigned long long seed = P.seed, t = (unsigned long long)token_index<ROWS, SLOTS>(c, id);
         const int i0 = blockIdx.x * kChunk + tid * kPerThread;
         uint32_t h[8];
         load8(c, row, i0, h);
-        if constexpr (PROC) process8<ROWS>(c, P, row, i0, eos_on, h);
+        if constexpr (PROC) process8<ROWS, SLOTS>(c, P, id, i0, eos_on, h);
         const uint32_t lo_key = topp ? (S.bin_p << 8) : S.tau_k;
         const uint32_t tau = lo_key > S.tau_k ? lo_key : S.tau_k;
         unsigned long long best = 0;
@@ -589,7 +653,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC, ROWS> c, int
                 any |= kk[j] >= tau;
             }
             if (!any) continue;
-            unsigned long long ctr[4] = {t, (unsigned long long)row, (unsigned long long)((i0 >> 2) + q), 0ull};
+            unsigned long long ctr[4] = {t, (unsigned long long)id.own, (unsigned long long)((i0 >> 2) + q), 0ull};
             philox4x64_10(ctr, seed, 0ull);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -630,7 +694,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC, ROWS> c, int
     if (tid == 0) st(&w->best_above, 0ull);
     if (tid >= 64) return;
     if (S.mode != MODE_LIVE) {
-        if (tid == 0) finish_row<PROC, ROWS>(c, row, P, (int64_t)P.pad, false);
+        if (tid == 0) finish_row<PROC, ROWS, SLOTS>(c, row, P, (int64_t)P.pad, false);
         return;
     }
     uint32_t lo_p = 0;
@@ -648,7 +712,7 @@ __global__ __launch_bounds__(kThreads) void sample_pass3(CtxT<PROC, ROWS> c, int
     best = above_best > best ? above_best : best;
     if (tid == 0) {
         if (!best) set_status(c, row);
-        finish_row<PROC, ROWS>(c, row, P, best ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, best != 0);
+        finish_row<PROC, ROWS, SLOTS>(c, row, P, best ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : (int64_t)P.pad, best != 0);
     }
 }
 
@@ -691,15 +755,17 @@ int sample_ctx(const A* a, Ctx* c) {
     return AWQ_OK;
 }
 
-template <bool PROC, bool ROWS = false, typename A>
-int sample_run(const A* a, const CtxT<PROC, ROWS>& c) {
+// grid: chunks x rows; the slots form (a->T: AwqSampleSlotsArgs) chunks x T x B
+template <bool PROC, bool ROWS = false, bool SLOTS = false, typename A>
+int sample_run(const A* a, const CtxT<PROC, ROWS, SLOTS>& c) {
     const hipStream_t s = static_cast<hipStream_t>(a->stream);
     const int greedy = (a->flags & AWQ_SAMPLE_FLAG_GREEDY) != 0;
-    const dim3 grid((unsigned)((a->V + kChunk - 1) / kChunk), (unsigned)a->B);
-    hipLaunchKernelGGL((sample_pass1<PROC, ROWS>), grid, dim3(kThreads), 0, s, c, greedy);
+    dim3 grid((unsigned)((a->V + kChunk - 1) / kChunk), (unsigned)a->B);
+    if constexpr (SLOTS) grid = dim3(grid.x, (unsigned)a->T, (unsigned)a->B);
+    hipLaunchKernelGGL((sample_pass1<PROC, ROWS, SLOTS>), grid, dim3(kThreads), 0, s, c, greedy);
     if (!greedy) {
-        hipLaunchKernelGGL((sample_pass2<PROC, ROWS>), grid, dim3(kThreads), 0, s, c, 0);
-        hipLaunchKernelGGL((sample_pass3<PROC, ROWS>), grid, dim3(kThreads), 0, s, c, 0);
+        hipLaunchKernelGGL((sample_pass2<PROC, ROWS, SLOTS>), grid, dim3(kThreads), 0, s, c, 0);
+        hipLaunchKernelGGL((sample_pass3<PROC, ROWS, SLOTS>), grid, dim3(kThreads), 0, s, c, 0);
     }
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;
 }
@@ -760,6 +826,48 @@ int awq_sample_tokens_rows(const AwqSampleRowsArgs* a) {
     c.history = a->history;
     c.history_stride = a->history_stride;
     return sample_run<true, true>(a, c);
+}
+
+int awq_sample_tokens_slots(const AwqSampleSlotsArgs* a) {
+    if (!a) return AWQ_ERR_NULL;
+    if (a->struct_bytes != sizeof(AwqSampleSlotsArgs)) return AWQ_ERR_BAD_SHAPE;
+    if (a->T < 2 || a->T > 8 || a->B < 1 || a->B * a->T > kMaxRows || a->V < 1 || a->V > kMaxVocab) return AWQ_ERR_UNSUPPORTED;
+    const int64_t rows = a->B * a->T;
+    if (a->row_stride < a->V) return AWQ_ERR_BAD_SHAPE;  // (rows >= 2)
+    if (!a->logits || !a->params || !a->cnt || !a->tok || !a->pred || !a->status || !a->workspace) return AWQ_ERR_NULL;
+    if (a->workspace_bytes < awq_sample_workspace_bytes(rows, a->V)) return AWQ_ERR_WORKSPACE;
+    if (((uintptr_t)a->workspace & 255u) != 0) return AWQ_ERR_BAD_ALIGNMENT;
+    if (((uintptr_t)a->logits & 1u) != 0) return AWQ_ERR_BAD_ALIGNMENT;
+    if (((uintptr_t)a->params & 7u) != 0 || ((uintptr_t)a->cnt & 3u) != 0 || ((uintptr_t)a->tok & 7u) != 0 ||
+        ((uintptr_t)a->pred & 7u) != 0 || ((uintptr_t)a->finished & 3u) != 0 || ((uintptr_t)a->status & 3u) != 0)
+        return AWQ_ERR_BAD_ALIGNMENT;
+    SlotsProcCtx c{};
+    c.logits = a->logits;
+    c.row_stride = a->row_stride;
+    c.V = (int)a->V;
+    c.B = (int)rows;
+    c.params = a->params;
+    c.out = a->pred;
+    c.out_stride = 1;
+    c.finished = const_cast<int32_t*>(a->finished);  // (read only: the slots kernels never latch)
+    c.status = a->status;
+    c.ws = static_cast<char*>(a->workspace);
+    c.cnt = a->cnt;
+    c.tok = a->tok;
+    if (!a->proc && !a->history) {
+        SlotsCtx r{};
+        static_cast<Ctx&>(r) = c;
+        r.cnt = a->cnt;
+        r.tok = a->tok;
+        return sample_run<false, false, true>(a, r);
+    }
+    if (!a->proc || !a->history) return AWQ_ERR_NULL;  // they go together
+    if (a->history_stride < (a->V + 31) / 32) return AWQ_ERR_BAD_SHAPE;
+    if (((uintptr_t)a->history & 3u) != 0 || ((uintptr_t)a->proc & 15u) != 0) return AWQ_ERR_BAD_ALIGNMENT;
+    c.proc = a->proc;
+    c.history = const_cast<uint32_t*>(a->history);    // (read only)
+    c.history_stride = a->history_stride;
+    return sample_run<true, false, true>(a, c);
 }
 
 int awq_sample_history_seed(uint32_t* history, int64_t history_stride, const int64_t* ids, int64_t ids_stride, int64_t B,

@@ -1,4 +1,4 @@
-// spec.hip -- the integer half of speculative decoding (awq_spec_accept, awq_ngram_draft; include/awq_hip.h): which of a verify
+// spec.hip -- the integer half of speculative decoding (awq_spec_accept / awq_spec_accept_ex, awq_ngram_draft; include/awq_hip.h): which of a verify
 // step's T tokens a row keeps, and the next step's drafts by prompt lookup.  One block per sequence, no host involvement,
 // capturable; every word lives in device memory the decoder owns (modules/fused/decode.py), the parameters in struct
 // AwqSpecParams there, so one captured launch serves every call.  tests/spec_ref.py restates both rules in numpy; the kernels
@@ -22,6 +22,9 @@ struct SpecWords {
     const uint32_t* status;
     int32_t* steps;
     int T, hist_cap, ring_cap;
+    uint32_t* history;  // awq_spec_accept_ex: the sampler's penalty bitmap [B, history_stride], or NULL
+    int64_t history_stride;
+    int V;
 };
 
 // Acceptance: a handful of words per row -- thread 0 of the row's block walks the T slots.
@@ -54,6 +57,7 @@ __global__ __launch_bounds__(64) void awq_spec_accept_kernel(SpecWords w) {
         const int tk = (int)pred[m];
         if (cnt + m < w.ring_cap) w.ring[(int64_t)b * w.ring_cap + cnt + m] = tk;
         if (nh + m >= 0 && nh + m < w.hist_cap) w.hist[(int64_t)b * w.hist_cap + nh + m] = tk;
+        if (w.history && tk >= 0 && tk < w.V) w.history[(int64_t)b * w.history_stride + (tk >> 5)] |= 1u << (tk & 31);  // (the row's one writer)
         ++m;
         for (int e = 0; e < n_eos; ++e) done |= tk == P.eos[e];
         done |= m >= budget;
@@ -117,15 +121,27 @@ int spec_words(const AwqSpecArgs* a, bool accept, SpecWords* w) {
     if (!a->params || !a->tok || !a->hist || !a->n_hist) return AWQ_ERR_NULL;
     if (accept && (!a->pred || !a->cnt || !a->ring || !a->finished || !a->pos_rows || !a->len_rows)) return AWQ_ERR_NULL;
     *w = SpecWords{a->params, a->tok, a->pred, a->hist, a->n_hist, a->cnt, a->ring, a->finished, a->pos_rows, a->len_rows,
-                   a->status, a->steps, (int)a->T, (int)a->hist_cap, (int)a->ring_cap};
+                   a->status, a->steps, (int)a->T, (int)a->hist_cap, (int)a->ring_cap, nullptr, 0, 0};
     return AWQ_OK;
 }
 
 }  // namespace
 
-int awq_spec_accept(const AwqSpecArgs* a) {
+int awq_spec_accept(const AwqSpecArgs* a) { return awq_spec_accept_ex(a, nullptr); }
+
+int awq_spec_accept_ex(const AwqSpecArgs* a, const AwqSpecHistoryArgs* q) {
     SpecWords w;
     if (int rc = spec_words(a, true, &w)) return rc;
+    if (q) {
+        if (q->struct_bytes != sizeof(AwqSpecHistoryArgs)) return AWQ_ERR_BAD_SHAPE;
+        if (q->flags != 0 || q->V < 1 || q->V > (1 << 20)) return AWQ_ERR_UNSUPPORTED;
+        if (!q->history) return AWQ_ERR_NULL;
+        if (q->history_stride < (q->V + 31) / 32) return AWQ_ERR_BAD_SHAPE;
+        if (((uintptr_t)q->history & 3u) != 0) return AWQ_ERR_BAD_ALIGNMENT;
+        w.history = q->history;
+        w.history_stride = q->history_stride;
+        w.V = (int)q->V;
+    }
     if (a->B == 0) return AWQ_OK;
     hipLaunchKernelGGL(awq_spec_accept_kernel, dim3((unsigned)a->B), dim3(64), 0, static_cast<hipStream_t>(a->stream), w);
     return hipGetLastError() == hipSuccess ? AWQ_OK : AWQ_ERR_LAUNCH;

@@ -36,6 +36,8 @@ behind the scalar call and the call with per-row arguments.  The families, what 
                                             rows_gen_graphs[bound]         generate, per-row arguments       step + rows sampler
                                             spec_graphs[(bound, T)]        generate(draft_tokens=T - 1)      verify step + argmax +
                                                                                                              accept + draft
+                                            spec_sample_graphs[(bound, T)] ... draft_accept="sampler"        verify step + slots
+                                                                                                             sampler + accept + draft
                                             verify_graphs[(bound, T)]      verify                            verify step
     lp_gen_graphs[(bound, (greedy, proc))]  row_lp_gen_graphs[...]         generate(logprobs=True)           step + sampler + log-prob
                                             row_lp_gen_graphs[(bound,      ... with per-row arguments        step + rows sampler +
@@ -77,6 +79,15 @@ step without the two integer kernels, for callers with drafts of their own.  dra
 
     out = dec.generate(ids, max_new_tokens=128, draft_tokens=3, draft_ngram=3)   # the text of the plain greedy run
     dec.last_spec                                                                 # {"replays": r, "new_tokens": [n_b ...]}
+
+draft_accept="sampler": the same loop with sampling and the logit processors.  The sampler's token is a deterministic function of the
+logits, (seed, token index, row) and the processors' state, so the graph (family `spec_sample_graphs`, device words of its own:
+`_spec_sample`) asks the sampler's slots form (awq_sample_tokens_slots) which token the plain sampler would emit at every slot's
+token index given the drafts before it, and awq_spec_accept_ex keeps a draft exactly when it is that token -- for a point-mass draft
+the acceptance probability p(draft) of rejection sampling -- and extends the penalty history by what was emitted.  The text is the
+plain sampled run's, token for token.  The default draft_accept="argmax" runs the graphs and launches above, unchanged.
+
+    out = dec.generate(ids, max_new_tokens=128, do_sample=True, temperature=0.7, seed=1, draft_tokens=3, draft_accept="sampler")
 
 Prefill at per-row positions (`extend`, `reset_rows`, `generate(extend=True)`): eager, no graph family.  `extend` appends row b's
 tokens at ITS position (rope + append with per-row counts, then csrc/prefill_attn.hip's rows form) and leaves the decoder in
@@ -152,6 +163,8 @@ class GraphedDecoder:
         self.spec_graphs = {}    # speculative decoding: (bucket bound, T) -> (graph, logits): verify step + argmax + accept + draft
         self.verify_graphs = {}  # (bucket bound, T) -> (graph, logits): the verify step alone (`verify`)
         self._spec = {}          # T -> the device words of the speculative path (allocated by its first use)
+        self.spec_sample_graphs = {}  # draft_accept="sampler": (bucket bound, T) -> (graph, logits): verify step + slots sampler + accept + draft
+        self._spec_sample = {}   # ... and its device words per T: those of `_spec` (addresses of their own) + params / proc / history per row
         self._verify_T = None    # tokens appended by the last `verify`, until `advance_rows`
         self.last_spec = None
         self.lp_gen_graphs = {}      # generate(logprobs=True): (bucket bound, (greedy, proc)) -> (graph, logits): step + sampler + log-prob
@@ -379,13 +392,15 @@ class GraphedDecoder:
         return logits
 
     def _spec_body(self, capturing, st, full):
-        """the verify step; full: + argmax, and -- recorded only, they move the decoder's words -- accept and draft"""
+        """the verify step; full: + the slots' tokens (argmax, or the slots sampler on the words of draft_accept="sampler"), and --
+        recorded only, they move the decoder's words -- accept and draft"""
         logits = self.lm.verify(st["tok"])
         if full:
             self._spec_tail(st, logits)
             if capturing:
+                more = {"history": st["history"], "vocab": st["vocab"]} if "history" in st else {}
                 ops.spec_accept(st["params"], st["tok"], st["pred"], st["hist"], st["n_hist"], st["cnt"], st["ring"],
-                                st["finished"], self.pos_rows, self.len_rows, status=st["status"], steps=st["steps"])
+                                st["finished"], self.pos_rows, self.len_rows, status=st["status"], steps=st["steps"], **more)
                 ops.ngram_draft(st["params"], st["tok"], st["hist"], st["n_hist"])
         return logits
 
@@ -613,10 +628,13 @@ class GraphedDecoder:
             raise NotImplementedError("speculative decoding: fuse_mixtral models are refused (the MoE block under a verify step "
                                       "is not covered by tests)")
 
-    def _spec_state(self, T, vocab=None, ring_cap=0, hist_cap=0):
+    def _spec_state(self, T, vocab=None, ring_cap=0, hist_cap=0, sampler=False):
         """The device words of the speculative path for steps of T tokens; their addresses are baked into the graphs of that T,
-        which are dropped when the words have to be reallocated (another vocabulary, a longer ring or history)."""
-        st = self._spec.get(T)
+        which are dropped when the words have to be reallocated (another vocabulary, a longer ring or history).  sampler: the
+        words of draft_accept="sampler" -- the same set at addresses of its own, and the slots sampler's per-row params / proc /
+        history; the greedy path's words and graphs are not touched."""
+        store = self._spec_sample if sampler else self._spec
+        st = store.get(T)
         if st is not None and (vocab is None or st["vocab"] == vocab) and st["ring"].shape[1] >= ring_cap and st["hist"].shape[1] >= hist_cap:
             return st
         if vocab is None:
@@ -637,19 +655,33 @@ class GraphedDecoder:
                   "ring": torch.zeros((B, max(int(ring_cap), 256)), dtype=torch.int32, device=dev),
                   "finished": torch.zeros(B, dtype=torch.int32, device=dev),
                   "steps": torch.zeros(B, dtype=torch.int32, device=dev)}
-        self.spec_graphs = {k: v for k, v in self.spec_graphs.items() if k[1] != T}
-        self.verify_graphs = {k: v for k, v in self.verify_graphs.items() if k[1] != T}
-        self._spec[T] = st
+            if sampler:
+                st.update({"sparams": torch.zeros((B, 64), dtype=torch.uint8, device=dev),   # struct AwqSampleParams [B]
+                           "proc": torch.zeros((B, 16), dtype=torch.uint8, device=dev),      # struct AwqSampleProc [B]
+                           "history": torch.zeros((B, ops.sample_history_words(vocab)), dtype=torch.int32, device=dev)})
+        if sampler:
+            self.spec_sample_graphs = {k: v for k, v in self.spec_sample_graphs.items() if k[1] != T}
+        else:
+            self.spec_graphs = {k: v for k, v in self.spec_graphs.items() if k[1] != T}
+            self.verify_graphs = {k: v for k, v in self.verify_graphs.items() if k[1] != T}
+        store[T] = st
         return st
 
     def _spec_tail(self, st, logits):
-        """the greedy argmax of the B * T slots: the sampler itself (its tie and NaN / +inf rules), no ring, no flags, no EOS ids"""
+        """The token of each of the B * T slots.  Greedy: the argmax by the sampler itself (its tie and NaN / +inf rules), no ring,
+        no flags, no EOS ids.  draft_accept="sampler": the slots form -- what the plain sampler would emit at the slot's token
+        index after the drafts before it; it writes pred and status alone, so the warm-up may run it."""
+        if "sparams" in st:
+            ops.sample_launch_slots(logits, st["sparams"], st["cnt"], st["tok"], st["pred"], st["status"], st["ws"],
+                                    finished=st["finished"], proc=st["proc"], history=st["history"])
+            return
         ops.sample_launch(logits.view(-1, logits.shape[-1]), st["argmax_params"], st["t"], st["pred"], st["status"], st["ws"],
                           greedy=True)
 
-    def _replay_spec(self, bound, T, full):
-        graph, logits = self._graph(self.spec_graphs if full else self.verify_graphs, (bound, T), bound, True, False, self._spec_body,
-                                    self._spec[T], full)
+    def _replay_spec(self, bound, T, full, sampler=False):
+        family = self.spec_sample_graphs if sampler else self.spec_graphs if full else self.verify_graphs
+        graph, logits = self._graph(family, (bound, T), bound, True, False, self._spec_body,
+                                    (self._spec_sample if sampler else self._spec)[T], full)
         self._replay(graph)
         return logits
 
@@ -686,7 +718,9 @@ class GraphedDecoder:
         self._verify_T = None
         self.seek_rows([p + c for p, c in zip(self.positions, counts)])
 
-    def _generate_spec(self, input_ids, max_new_tokens, K, ngram, eos, pad_token_id, check_every, attention_mask):
+    def _generate_spec(self, input_ids, max_new_tokens, K, ngram, eos, pad_token_id, check_every, attention_mask, sampler=None):
+        """The speculative run.  sampler: None (greedy: the slots' argmax), or the sampling arguments of draft_accept="sampler" --
+        token 1 by the plain sampler with the processors, the slots by its slots form; everything else is shared."""
         T = K + 1
         self._spec_check_model(T)
         B, S = input_ids.shape
@@ -699,8 +733,17 @@ class GraphedDecoder:
         params = ops.spec_params(eos_ids=eos, pad=pad, max_new_tokens=max_new_tokens, ngram_max=ngram)
         # always per-row: equal positions diverge at the first step (unpadded: the shared position is every row's length)
         logits, _ = self._first_logits(input_ids, attention_mask, per_row=True)
-        st = self._spec_state(T, logits.shape[-1], max_new_tokens, max(lengths) + max_new_tokens)
-        first = ops.sample_tokens(logits, do_sample=False)  # token 1, eagerly (raises on NaN / +inf logits)
+        st = self._spec_state(T, logits.shape[-1], max_new_tokens, max(lengths) + max_new_tokens, sampler=sampler is not None)
+        if sampler is None:
+            first = ops.sample_tokens(logits, do_sample=False)  # token 1, eagerly (raises on NaN / +inf logits)
+        else:
+            # the plain path's start: the history holds input_ids as passed, token 1 is the plain sampler's at t = 1 (row b keys
+            # its Philox counter, as request b keys the slots'), which also adds it to the history
+            st["sparams"].copy_(ops.sample_params_rows(B, eos_ids=eos, pad=pad, **sampler["params"]))
+            st["proc"].copy_(ops.sample_proc_params_rows(B, **sampler["proc"]))
+            st["history"].zero_()
+            ops.sample_history(input_ids, st["vocab"], out=st["history"])
+            first = ops.sample_tokens(logits, t=1, eos_ids=eos, pad=pad, history=st["history"], **sampler["params"], **sampler["proc"])
         # reset the decoder-owned words outside any capture: prompt and token 1 into the history, token 1 into the ring
         n_hist = torch.tensor(lengths, dtype=torch.int64, device=self.device)
         st["params"].copy_(params)
@@ -726,13 +769,13 @@ class GraphedDecoder:
                 if all(words[:B]):
                     break
                 upper = words[B:]
-            self._replay_spec(self.bucket(min(max(upper) + T, self.max_seq_len)), T, full=True)
+            self._replay_spec(self.bucket(min(max(upper) + T, self.max_seq_len)), T, full=True, sampler=sampler is not None)
             upper = [u + T for u in upper]
             replays += 1
         words = torch.cat([st["finished"], self.pos_rows, st["cnt"], st["steps"], st["status"]]).cpu().tolist()
         bad = sorted({r // T for r in range(B * T) if (words[4 * B + r // 32] >> (r % 32)) & 1})
         if bad:
-            raise AwqHipError(f"generate: rows {bad} produced NaN / +inf logits")
+            raise AwqHipError(f"generate: rows {bad} produced NaN / +inf logits" + (" or kept no token" if sampler is not None else ""))
         cnt = words[2 * B:3 * B]
         self.seek_rows(words[B:2 * B])
         # replays: those the slowest row needed (the host may have launched a few more before its next look at the flags)
@@ -774,7 +817,7 @@ class GraphedDecoder:
     @torch.inference_mode()
     def generate(self, input_ids, max_new_tokens, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=0,
                  eos_token_id=None, pad_token_id=None, check_every=16, attention_mask=None, repetition_penalty=1.0,
-                 min_new_tokens=0, draft_tokens=0, draft_ngram=3, extend=False, logprobs=False):
+                 min_new_tokens=0, draft_tokens=0, draft_ngram=3, extend=False, logprobs=False, draft_accept="argmax"):
         """input_ids [batch, prompt] -> [batch, prompt + n] int64 on the device, n <= max_new_tokens; rows that emitted an EOS id
         are padded with pad_token_id (default: the first EOS id) from then on, and the run stops once every row has (HF's
         `generate` semantics).  The prompt is prefilled eagerly and token 1 sampled eagerly from its last position; every later
@@ -791,9 +834,19 @@ class GraphedDecoder:
         draft_tokens = K in 1 .. 7 (0 = off): greedy speculative decoding by prompt lookup (transformers'
         `prompt_lookup_num_tokens`) -- every replay verifies K drafts found by matching the row's last draft_ngram .. 1 tokens
         earlier in its own text and emits 1 .. K + 1 tokens; the text is the plain greedy run's (up to ties the two launch shapes
-        round differently).  `last_spec` then holds {"replays": those the slowest row needed, "new_tokens": per row, "launched"}.  Greedy only (do_sample with temperature > 0,
-        repetition_penalty != 1 and min_new_tokens > 0 raise ValueError; an fp8 cache NotImplementedError), and no window roll:
-        prompt + max_new_tokens + K + 1 <= max_seq_len for every row.
+        round differently).  `last_spec` then holds {"replays": those the slowest row needed, "new_tokens": per row, "launched"}.  With the default
+        draft_accept="argmax" this is greedy only (do_sample with temperature > 0, repetition_penalty != 1 and min_new_tokens > 0
+        raise ValueError).  An fp8 cache raises NotImplementedError, and there is no window roll: prompt + max_new_tokens + K + 1 <=
+        max_seq_len for every row.
+        draft_accept="sampler" (needs draft_tokens >= 1): speculative decoding with scalar do_sample, temperature, top_k, top_p,
+        seed, repetition_penalty and min_new_tokens.  The sampler's token is a deterministic function of the logits, (seed, token
+        index, row) and the processors' state, so every slot of a verify step asks which token the plain sampler would emit at its
+        token index given the drafts before it (ops.sample_tokens_slots), and a draft is accepted exactly when it is that token --
+        with probability p(draft), the acceptance probability of rejection sampling for a point-mass draft.  Row b's tokens are those
+        of `generate` without draft_tokens and with the same arguments, except at positions where the two launch shapes round the
+        logits differently.  Graphs and device words of its own (`spec_sample_graphs`); a call with "argmax" and a plain call run
+        exactly the graphs they ran before.  Not with per-row arguments, extend=True or logprobs=True (ValueError), an fp8 cache or
+        a fuse_mixtral model (NotImplementedError); any other value of draft_accept raises ValueError.
         extend=True: input_ids / attention_mask (a row may be all zeros) are APPENDED to each row's context instead of
         restarting it -- the next turn of a conversation.  Every row goes back to what the previous call left in its cache
         (`tail`: its prompt and the real tokens it was fed; the pads fed to a finished row are dropped), the last token that call
@@ -818,6 +871,10 @@ class GraphedDecoder:
         if input_ids.dim() != 2 or input_ids.shape[0] != self.batch:
             raise ValueError(f"input_ids must be [{self.batch}, prompt], got {tuple(input_ids.shape)}")
         logprobs = bool(logprobs)
+        if draft_accept not in ("argmax", "sampler"):
+            raise ValueError(f'generate: draft_accept must be "argmax" or "sampler", got {draft_accept!r}')
+        if draft_accept == "sampler" and not draft_tokens:
+            raise ValueError('generate: draft_accept="sampler" needs draft_tokens >= 1 (it names how drafts are accepted)')
         if logprobs and draft_tokens:
             raise ValueError("generate: logprobs is not available with draft_tokens (a speculative step emits a variable number "
                              "of tokens per replay)")
@@ -841,6 +898,13 @@ class GraphedDecoder:
         if draft_tokens:
             if isinstance(draft_tokens, bool) or int(draft_tokens) != draft_tokens or not 1 <= int(draft_tokens) <= 7:
                 raise ValueError(f"draft_tokens must be an integer in 0 .. 7, got {draft_tokens}")
+            if draft_accept == "sampler":
+                sampler = {"params": {"do_sample": do_sample, "temperature": temperature, "top_k": top_k, "top_p": top_p, "seed": seed},
+                           "proc": {"repetition_penalty": repetition_penalty, "min_new_tokens": min_new_tokens}}
+                ops.sample_params(eos_ids=eos, pad=pad_token_id, **sampler["params"])  # the checks of the values, before any launch
+                ops.sample_proc_params(**sampler["proc"])
+                return self._generate_spec(input_ids, max_new_tokens, int(draft_tokens), int(draft_ngram), eos, pad_token_id,
+                                           check_every, attention_mask, sampler=sampler)
             if do_sample and float(temperature) > 0:
                 raise ValueError("speculative decoding is greedy: do_sample with temperature > 0 needs rejection sampling")
             if float(repetition_penalty) != 1.0 or int(min_new_tokens) > 0:

@@ -1407,6 +1407,102 @@ def sample_tokens_rows(logits, *, do_sample, temperature=1.0, top_k=0, top_p=1.0
                           history, max_new=max_rows)
 
 
+# ---- the sampler over the slots of a verify step (awq_sample_tokens_slots) --------------------------------------------------------
+
+def sample_launch_slots(logits, params, cnt, tok, pred, status, workspace, finished=None, greedy=False, proc=None, history=None):
+    """The raw launch of awq_sample_tokens_slots (no validation of the configuration, no sync): logits fp16 [B, T, V] or
+    [B * T, V], row b * T + j the slot j of request b; params (uint8 [B, 64], sample_params_rows), cnt (int32 [B]: tokens generated
+    so far), tok (int64 [B, T]: the step's input -- the last token, then the drafts), pred (int64 [B * T]: the slots' tokens),
+    status (int32, ceil(B * T / 32) words), workspace (sample_workspace_bytes(B * T, V), zeroed once), finished (int32 [B],
+    optional); proc (uint8 [B, 16]) with history (int32 [B, >= ceil(V / 32)]).  Slot (b, j) gets the token the rows form emits for
+    request b at token index cnt[b] + 1 + j with tok[b, 1 .. j] added to the seen ids.  Only pred and status are written.
+    Capturable."""
+    fn = "sample_launch_slots"
+    if tok is None or tok.dim() != 2 or tok.dtype != torch.int64 or not tok.is_contiguous():
+        raise _lib.AwqHipError(f"{fn}: tok must be a contiguous int64 [B, T] tensor")
+    B, T = tok.shape
+    if logits.dtype != torch.float16 or logits.dim() not in (2, 3):
+        raise _lib.AwqHipError(f"{fn}: fp16 logits [B, T, V] or [B * T, V] expected, got {logits.dtype} {tuple(logits.shape)}")
+    rows = logits.reshape(-1, logits.shape[-1]) if logits.dim() == 3 else logits
+    if rows.stride(1) != 1:
+        rows = rows.contiguous()
+    if rows.shape[0] != B * T:
+        raise _lib.AwqHipError(f"{fn}: {rows.shape[0]} logits rows for {B} x {T} slots")
+    V = rows.shape[1]
+    _require_gpu(rows, params, cnt, tok, pred, status, workspace, finished, proc, history)
+    if (proc is None) != (history is None):
+        raise _lib.AwqHipError(f"{fn}: proc and history go together")
+    if history is not None and (history.dtype != torch.int32 or history.dim() != 2 or history.shape[0] != B
+                                or history.shape[1] < sample_history_words(V) or history.stride(1) != 1):
+        raise _lib.AwqHipError(f"{fn}: history must be int32 [{B}, >= {sample_history_words(V)}] with unit column stride")
+    if not params.is_contiguous() or params.numel() * params.element_size() < B * ctypes.sizeof(_lib.AwqSampleParams):
+        raise _lib.AwqHipError(f"{fn}: params must hold {B} x 64 contiguous bytes (sample_params_rows)")
+    if proc is not None and (not proc.is_contiguous() or proc.numel() * proc.element_size() < B * ctypes.sizeof(_lib.AwqSampleProc)):
+        raise _lib.AwqHipError(f"{fn}: proc must hold {B} x 16 contiguous bytes (sample_proc_params_rows)")
+    if pred.dtype != torch.int64 or pred.numel() < B * T or not pred.is_contiguous():
+        raise _lib.AwqHipError(f"{fn}: pred must be a contiguous int64 tensor of B * T elements")
+    if status.dtype != torch.int32 or status.numel() * 32 < B * T:
+        raise _lib.AwqHipError(f"{fn}: status must hold one bit per (row, slot)")
+    for name, w in (("cnt", cnt), ("finished", finished)):
+        if w is not None and (w.dtype != torch.int32 or w.numel() < B or not w.is_contiguous()):
+            raise _lib.AwqHipError(f"{fn}: {name} must be a contiguous int32 [{B}] tensor")
+    a = _lib.AwqSampleSlotsArgs()
+    a.struct_bytes = ctypes.sizeof(a)
+    a.flags = SAMPLE_FLAG_GREEDY if greedy else 0
+    a.logits, a.B, a.T, a.V, a.row_stride = _ptr(rows), B, T, V, rows.stride(0)
+    a.params, a.cnt, a.tok, a.pred = _ptr(params), _ptr(cnt), _ptr(tok), _ptr(pred)
+    a.finished, a.status = _ptr(finished), _ptr(status)
+    a.workspace, a.workspace_bytes = _ptr(workspace), workspace.numel()
+    a.proc, a.history, a.history_stride = _ptr(proc), _ptr(history), history.stride(0) if history is not None else 0
+    with torch.cuda.device(rows.device):
+        a.stream = _stream()
+        rc = _lib.lib().awq_sample_tokens_slots(ctypes.byref(a))
+    _lib.check(rc, "awq_sample_tokens_slots")
+    return pred
+
+
+def sample_tokens_slots(logits, tok, cnt, *, do_sample, temperature=1.0, top_k=0, top_p=1.0, seed=0, eos_ids=(), pad=None,
+                        repetition_penalty=1.0, min_new_tokens=0, history=None, finished=None, status=None, greedy=False):
+    """The tokens of the B x T slots of a verify step (see sample_launch_slots): logits fp16 [B, T, V], tok int64 [B, T] and cnt
+    int32 [B] on the device; the sampling arguments and processors per request as in sample_tokens_rows (a scalar, or a sequence
+    of B values).  Returns pred int64 [B, T]: slot (b, j) is the token sample_tokens_rows emits for request b at t = cnt[b] + 1 + j
+    with the drafts tok[b, 1 .. j] added to its history.  Nothing but the result (and `status`) is written.  Without `status` the
+    call waits for the result and raises AwqHipError if a slot held NaN / +inf or kept nothing.  greedy: force the argmax."""
+    if tok.dim() != 2:
+        raise ValueError("sample_tokens_slots: tok must be [B, T]")
+    B, T = tok.shape
+    params = sample_params_rows(B, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                eos_ids=eos_ids, pad=pad)
+    proc = sample_proc_params_rows(B, repetition_penalty, min_new_tokens)
+    pens, mins = per_row("repetition_penalty", repetition_penalty, B), per_row("min_new_tokens", min_new_tokens, B)
+    if any(float(p) != 1.0 for p in pens) and history is None:
+        raise ValueError("sample_tokens_slots: repetition_penalty needs a history of the ids seen (sample_history)")
+    use_proc = history is not None or any(int(m) > 0 for m in mins)
+    _require_gpu(logits, tok, cnt)
+    V, dev = logits.shape[-1], logits.device
+    need = sample_workspace_bytes(B * T, V)
+    if need == 0:
+        err = _lib.AwqHipError(f"sample_tokens_slots: no kernel for B * T = {B * T}, V = {V} (limits B * T <= 1024, V <= 2^20)")
+        err.code = _lib.ERR_UNSUPPORTED
+        raise err
+    with torch.cuda.device(dev):
+        pred = torch.empty(B * T, dtype=torch.int64, device=dev)
+        own_status = status is None
+        if own_status:
+            status = torch.zeros((B * T + 31) // 32, dtype=torch.int32, device=dev)
+        proc_d = hist = None
+        if use_proc:
+            proc_d = proc.to(dev)
+            hist = history if history is not None else torch.zeros((B, sample_history_words(V)), dtype=torch.int32, device=dev)
+        sample_launch_slots(logits, params.to(dev), cnt, tok, pred, status, _sample_workspace(dev, need), finished=finished,
+                            greedy=greedy, proc=proc_d, history=hist)
+        if own_status and bool(status.any()):
+            st = status.cpu().tolist()
+            bad = [(r // T, r % T) for r in range(B * T) if (st[r // 32] >> (r % 32)) & 1]
+            raise _lib.AwqHipError(f"sample_tokens_slots: slots {bad} hold NaN / +inf logits or keep no token (emitted pad)")
+    return pred.view(B, T)
+
+
 # ---- speculative decoding: the verify step's attention (csrc/verify_attn.hip), acceptance and prompt-lookup drafts (csrc/spec.hip)
 
 _verify_workspaces = {}
@@ -1494,13 +1590,30 @@ def _spec_args(params, tok, hist, n_hist, pred=None, cnt=None, ring=None, finish
     return a
 
 
-def spec_accept(params, tok, pred, hist, n_hist, cnt, ring, finished, pos_rows, len_rows, status=None, steps=None):
+def spec_accept(params, tok, pred, hist, n_hist, cnt, ring, finished, pos_rows, len_rows, status=None, steps=None, history=None,
+                vocab=None):
     """awq_spec_accept on device words the caller owns (include/awq_hip.h states the rule; tests/spec_ref.py restates it).
-    Capturable, no sync."""
+    history (int32 [B, >= ceil(vocab / 32)], with vocab): awq_spec_accept_ex -- the bit of every emitted token is set in the
+    sampler's penalty history of its row.  Capturable, no sync."""
     a = _spec_args(params, tok, hist, n_hist, pred, cnt, ring, finished, pos_rows, len_rows, status, steps)
+    if history is None:
+        with torch.cuda.device(tok.device):
+            a.stream = _stream()
+            _lib.check(_lib.lib().awq_spec_accept(ctypes.byref(a)), "awq_spec_accept")
+        return
+    if vocab is None:
+        raise _lib.AwqHipError("spec_accept: history needs vocab")
+    _require_gpu(history)
+    if (history.dtype != torch.int32 or history.dim() != 2 or history.shape[0] != tok.shape[0]
+            or history.shape[1] < sample_history_words(vocab) or history.stride(1) != 1):
+        raise _lib.AwqHipError(f"spec_accept: history must be int32 [{tok.shape[0]}, >= {sample_history_words(vocab)}] with unit "
+                               "column stride")
+    q = _lib.AwqSpecHistoryArgs()
+    q.struct_bytes, q.flags = ctypes.sizeof(q), 0
+    q.history, q.history_stride, q.V = _ptr(history), history.stride(0), int(vocab)
     with torch.cuda.device(tok.device):
         a.stream = _stream()
-        _lib.check(_lib.lib().awq_spec_accept(ctypes.byref(a)), "awq_spec_accept")
+        _lib.check(_lib.lib().awq_spec_accept_ex(ctypes.byref(a), ctypes.byref(q)), "awq_spec_accept_ex")
 
 
 def ngram_draft(params, tok, hist, n_hist):

@@ -738,6 +738,50 @@ typedef struct AwqSampleRowsArgs {
 
 AWQ_EXPORT int awq_sample_tokens_rows(const AwqSampleRowsArgs* args);
 
+/* ---- the sampler over the slots of a speculative verify step (csrc/sample.hip, the SLOTS kernels) ---------------------------
+ * awq_sample_tokens_slots answers, for each of the T slots of each of B requests, "which token would awq_sample_tokens_rows emit
+ * for this request at this token index, given the drafts in front of the slot".  logits: fp16 [B * T, V] (row_stride elements
+ * apart); row r = b * T + j is slot j of request b.  Everything is read from DEVICE memory, so one captured launch serves every
+ * call: params [B], cnt [B] (int32: the tokens request b has generated so far -- the word awq_spec_accept maintains), tok [B, T]
+ * (int64: the step's input; tok[b, 0] is the request's last token, tok[b, 1 .. T - 1] its drafts) and, optionally and together,
+ * proc [B] with history [B, history_stride].  Slot (b, j):
+ *   - token index t = cnt[b] + 1 + j; Philox key (seed[b], 0), counter (t, b, i / 4, 0) -- the REQUEST b, not the launch row;
+ *   - greedy or sampled, temperature, top_k, top_p, EOS ids and pad as params[b] says; EOS suppression while t <= min_new_tokens[b];
+ *   - the repetition penalty over history row b OR the bits of tok[b, 1 .. j]: the drafts in front of the slot count as seen
+ *     (tok[b, 0] is in the history already); draft ids outside [0, V) are ignored;
+ *   - writes pred[r] (int64) and, for a NaN / +inf / nothing-kept row (which emits pad), the sticky bit r % 32 of status[r / 32]
+ *     -- and NOTHING else: cnt is not advanced, history, tok and finished are read only, there is no ring, no latch, no *t.
+ * finished (optional, [B]): the slots of a finished request are not sampled; they write pad and set no status bit.
+ * So pred[b * T + j] and its status bit are what awq_sample_tokens_rows emits for row b of a B-row launch whose logits row b is
+ * slot (b, j)'s row, with t[b] = cnt[b] + 1 + j, the same params[b] / proc[b] and history row b with the bits of tok[b, 1 .. j]
+ * ORed in -- bit for bit on any input (ties, -inf, tied boundary groups, bad rows): both run the same arithmetic.
+ * AWQ_SAMPLE_FLAG_GREEDY keeps its meaning.  Limits: 2 <= T <= 8, 1 <= B * T <= 1024, 1 <= V <= 2^20 (AWQ_ERR_UNSUPPORTED);
+ * validation order, alignment rules and error codes are those of awq_sample_tokens_rows (cnt 4-byte, tok and pred 8-byte aligned).
+ * The workspace is awq_sample_workspace_bytes(B * T, V) bytes and is left all zero. */
+typedef struct AwqSampleSlotsArgs {
+    uint32_t struct_bytes; /* sizeof(AwqSampleSlotsArgs) */
+    uint32_t flags;
+    const uint16_t* logits; /* [B * T, V] */
+    int64_t B;
+    int64_t T;
+    int64_t V;
+    int64_t row_stride;    /* elements */
+    const AwqSampleParams* params; /* [B] */
+    const int32_t* cnt;    /* [B] */
+    const int64_t* tok;    /* [B, T] */
+    int64_t* pred;         /* [B * T] */
+    const int32_t* finished; /* [B] or NULL */
+    uint32_t* status;      /* [ceil(B * T / 32)] */
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+    const AwqSampleProc* proc; /* [B] or NULL */
+    const uint32_t* history; /* [B, history_stride] or NULL (with proc) */
+    int64_t history_stride; /* words */
+} AwqSampleSlotsArgs;
+
+AWQ_EXPORT int awq_sample_tokens_slots(const AwqSampleSlotsArgs* args);
+
 /* ---- speculative decoding: a k-token verify step (csrc/verify_attn.hip) and prompt-lookup drafts (csrc/spec.hip) ---------------
  * awq_verify_attention_rows: attention of T = 2 .. 8 NEW tokens per sequence over the cache, at per-row device positions.
  *   q [B, T, n_heads, 128] fp16 is the q_out of awq_rope_kv_append_rows(S = T), which has ALREADY written cache rows
@@ -759,7 +803,8 @@ AWQ_EXPORT int awq_verify_attention_rows(const uint16_t* q, const uint16_t* k_ca
  * State per row b: hist [B, hist_cap] int32 (every token of the row by index: prompt, then generated), n_hist [B], cnt [B] (tokens
  * generated so far), ring [B, ring_cap] (the generated tokens), finished [B], pos_rows / len_rows [B], the step's input
  * tok [B, T] int64.  AwqSpecParams lives in DEVICE memory like AwqSampleParams.
- * awq_spec_accept (row not finished; in = tok[b, :], pred [B * T] int64 = the greedy argmax of the step's logits at each slot):
+ * awq_spec_accept (row not finished; in = tok[b, :], pred [B * T] int64 = the slot's token: what the sampler emits on the step's
+ *   logits at each slot -- the greedy argmax, or awq_sample_tokens_slots' token):
  *   a = the largest value in 0 .. T - 1 with in[j + 1] == pred[j] for all j < a; the new tokens are pred[0 .. a], cut after the
  *   first EOS id among them (inclusive) and at max_new_tokens - cnt[b]; m >= 1 of them remain.  They are appended to ring[b, cnt ..]
  *   and hist[b, n_hist ..] (writes past ring_cap / hist_cap are dropped); cnt, n_hist, pos_rows, len_rows += m; finished[b] = 1 if
@@ -802,6 +847,20 @@ typedef struct AwqSpecArgs {
 
 AWQ_EXPORT int awq_spec_accept(const AwqSpecArgs* args);
 AWQ_EXPORT int awq_ngram_draft(const AwqSpecArgs* args);
+
+/* awq_spec_accept_ex(args, history) is awq_spec_accept that also keeps the sampler's penalty history (the bitmap of
+ * awq_sample_tokens_ex): after row b's m tokens are appended to ring / hist, the bit of each of them is set in history row b (bit
+ * v % 32 of word v / 32; history_stride >= ceil(V / 32) words); ids outside [0, V) set nothing; a finished row, or one with a
+ * status bit, touches nothing.  history == NULL is exactly awq_spec_accept. */
+typedef struct AwqSpecHistoryArgs {
+    uint32_t struct_bytes; /* sizeof(AwqSpecHistoryArgs) */
+    uint32_t flags;        /* 0 (reserved) */
+    uint32_t* history;     /* [B, history_stride] */
+    int64_t history_stride; /* words */
+    int64_t V;
+} AwqSpecHistoryArgs;
+
+AWQ_EXPORT int awq_spec_accept_ex(const AwqSpecArgs* args, const AwqSpecHistoryArgs* history);
 
 /* ---- token log-probabilities (csrc/logprob.hip) -------------------------------------------------------------------------------
  * awq_token_logprobs: for each of R rows, out = (x[id] - m) - log sum_i exp(x_i - m) in fp32, x the row's V fp16 logits cast to
